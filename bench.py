@@ -6,9 +6,10 @@ Headline (the top-level fields): Quadrotor2D trajectory tracking (BASELINE confi
 quadrotor_2D/quadrotor_2D_track.yaml), 65 536 envs per GPU, float32.  One "step" = one control step of every env = ONE
 launch of the fused step kernel (action pre-processing, 20 engine substeps, observation / reward / done / info / 16
 constraint rows, episode statistics, auto-reset), synthetic actions ~U(-1,1) resident in HBM (the reference's own README
-benchmark is the same open-loop random-action loop on one env).  The K timed launches are one HIP graph; when K is small
-the K-step graph is replayed R times, each replay timed between barrier + synchronize, and the MEDIAN replay is reported
-(`config.timing`), so that K = 20 is not a single 0.1 ms sample.
+benchmark is the same open-loop random-action loop on one env).  Exactly K = --steps launches are timed, once, between
+barrier + synchronize, as replays of HIP graphs of up to --graph-len steps; `ms_per_step` is that region / K.
+`--dump-outputs DIR` writes what the last timed step returned to its caller (obs, reward, done, ... of every env; a fixed
+seeded sample of envs when that exceeds 64 MB) as DIR/<name>.npy; inputs are seeded, so two builds compare output for output.
 
 Secondary objects (rank 0, N = 1): `f64` (the float64 kernels of the same workload), `secondary` (the other BASELINE
 configs' env kernels: cartpole_stab incl. the fused random-action rollout of config #2, quadrotor_3D_track[_disturbed]),
@@ -83,6 +84,8 @@ def parse():
     ap.add_argument('--ppo-envs', type=int, default=65536, help='envs per GPU of the PPO leg (BASELINE config #3: 65 536)')
     ap.add_argument('--sac-seeds', type=int, default=3, help='seeds of the SAC wall-clock-to-reward leg on config #5 (0 = skip)')
     ap.add_argument('--sac-seconds', type=float, default=40.0, help='budget per seed')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the step outputs of the last timed step as DIR/<name>.npy (float32 / float64)')
     return ap.parse_args()
 
 
@@ -254,32 +257,52 @@ class StepBench:
         self.out, self.c_out = self.env.bind_outputs(state=None, noisy_action=None)
         self.G = graph_len
         self.graph = None
+        self.tails = {}             # k % G -> graph of the last k % G steps, so that do(k) runs exactly k steps
         if use_graph:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self._run(8)
             torch.cuda.current_stream().wait_stream(s)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._run(self.G)
+            self.graph = self._capture(self.G)
+
+    def _capture(self, k):
+        g = self.torch.cuda.CUDAGraph()
+        with self.torch.cuda.graph(g):
+            self._run(k)
+        return g
 
     def _run(self, k):
         for t in range(k):
             self.env.step_tensors(self.actions[t % self.ring], out=self.out, c_out=self.c_out)
 
+    def prepare(self, k):
+        """Capture the remainder graph do(k) needs (outside any timed region)."""
+        r = k % self.G
+        if self.graph is not None and r and r not in self.tails:
+            self.torch.cuda.synchronize()
+            self.tails[r] = self._capture(r)
+
     def do(self, k):
+        """Exactly k control steps: k // G replays of the G-step graph, then one replay of the (k % G)-step graph."""
         if self.graph is None:
             self._run(k)
             return k
-        reps = (k + self.G - 1) // self.G
-        for _ in range(reps):
+        for _ in range(k // self.G):
             self.graph.replay()
-        return reps * self.G
+        if k % self.G:
+            self.prepare(k)
+            self.tails[k % self.G].replay()
+        return k
+
+    def outputs(self):
+        """The arrays a caller of the step path receives after the last step, as {name: device tensor}."""
+        return {k: getattr(self.out, k) for k in type(self.out).__slots__ if getattr(self.out, k) is not None}
 
     def kernel_period_us(self, k):
         """Average launch-to-launch period of the step kernel over >= k launches (HIP events on the launch stream)."""
         torch = self.torch
+        self.prepare(k)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         ev0.record()
@@ -957,6 +980,32 @@ def sac_leg(torch, seeds, budget_s, envs=2048, batch=4096, updates_per_step=16, 
                      f'lr {lr:g}, warm-up {warm_up_steps} env steps, tau 0.005, alpha 0.2'}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, tensors, n, limit=DUMP_LIMIT_BYTES):
+    """Write {name: device tensor with one axis of n envs} as path/<name>.npy in the caller's layout (obs [n, obs_dim], c_values
+    [rows, n], ...): float tensors keep their dtype, integer / bool ones become float32.  When the arrays exceed `limit` bytes
+    together, the same fixed, seeded sample of envs is taken along every array's env axis, and its env indices are written as
+    env_index.npy (float64)."""
+    import numpy as np
+    arrs = {}
+    for k, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    if total > limit:
+        m = max(1, int(n * (limit - 8 * 4096) / (total + 8 * n)))      # room for env_index.npy and the .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        arrs = {k: np.ascontiguousarray(np.take(a, idx, axis=a.shape.index(n))) for k, a in arrs.items()}
+        arrs['env_index'] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f'{k}.npy'), a)
+    print(f'[bench] step outputs of the last timed step -> {path}: {", ".join(sorted(arrs))}'
+          + (f' (a seeded sample of {len(idx)} of {n} envs)' if total > limit else ''), file=sys.stderr)
+
+
 def self_spawn(args):
     """`python bench.py --gpus N` with N > 1 and no launcher environment: become the launcher.  Re-executes this file under
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` (one rank per
@@ -1039,19 +1088,17 @@ def main():
             dist.barrier()
         return el_s, n
 
+    hb.prepare(args.warmup)
+    hb.prepare(args.steps)
     hb.do(args.warmup)
-    # timed region: EXACTLY K steps between barrier + synchronize.  When K is small (one graph replay), the same K-step
-    # region is repeated and the median repeat is reported (every repeat is bracketed the same way).
-    repeats = 1 if args.steps >= 5000 else 31
-    samples, done_steps = [], args.steps
-    for _ in range(repeats):
-        el_s, done_steps = timed_region()
-        samples.append(el_s)
-    elapsed = statistics.median(samples)
+    # timed region: EXACTLY K = --steps steps, once, between barrier + synchronize
+    elapsed, done_steps = timed_region()
     el = torch.tensor([elapsed], device=dev if backend == 'nccl' else 'cpu', dtype=torch.float64)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hb.outputs(), N)      # what the last timed step left, before any further step
     period_us = hb.kernel_period_us(max(args.steps, 4000))      # launch period inside long back-to-back replays
     ok = hb.sane()
     value = world * N * done_steps / elapsed
@@ -1070,9 +1117,9 @@ def main():
                        'parallelism': f'env-shard x{world}', 'rccl_ranks': rccl_ranks, 'collective_backend': backend if world > 1 else None,
                        'finite_outputs': ok,
                        'kernel_build': 'config-specialised' if hb.env.specialized else 'generic',
-                       'timing': (f'median of {repeats} timed repeats of the {done_steps}-step region' if repeats > 1 else 'one timed region')
+                       'timing': f'one timed region of {done_steps} steps'
                                  + ('; per rank: barrier + synchronize, clock, K steps, synchronize, clock, barrier; MAX over ranks' if world > 1 else ''),
-                       'timed_region_samples_ms': [round(1e3 * s, 4) for s in (min(samples), elapsed, max(samples))]},
+                       'timed_region_ms': round(1e3 * elapsed, 4)},
             'roofline': roofline_of(args.task, args.dtype, N, period_us, driver_step_us=1e6 * elapsed / done_steps,
                                     geometry=launch_geometry(N, bool(hb.env.specialized), args.task)),
         }

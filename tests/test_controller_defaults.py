@@ -1,14 +1,14 @@
 """Controller registry (registration.py / controllers.py): the reference's controller ids resolve, and get_config(idx) returns
-the defaults of the reference's own controllers/<algo>/<algo>.yaml — compared against those files when the reference checkout
-is present (build container), against the pinned literal otherwise."""
+the defaults of the reference's own controllers/<algo>/<algo>.yaml — as recorded in tests/golden/controller_defaults.json
+(tests/golden/make_controller_defaults.py) — and the pinned literal."""
+import json
 import os
 
 import pytest
-import yaml
 
 from safe_control_gym_amd.registration import get_config, spec
 
-REF = '/root/reference/safe_control_gym/controllers'
+GOLDEN = json.load(open(os.path.join(os.path.dirname(__file__), 'golden', 'controller_defaults.json')))
 FILES = {'ppo': 'ppo/ppo.yaml', 'sac': 'sac/sac.yaml', 'rarl': 'rarl/rarl.yaml', 'rap': 'rarl/rap.yaml',
          'safe_explorer_ppo': 'safe_explorer/safe_ppo.yaml'}
 
@@ -18,11 +18,9 @@ def test_controller_ids_and_default_configs(idx):
     assert spec(idx).entry_point.startswith('safe_control_gym_amd.controllers:')
     cfg = get_config(idx)
     assert cfg is not get_config(idx)                       # a fresh copy per call, like the YAML loader
-    path = os.path.join(REF, FILES[idx])
-    if not os.path.exists(path):
-        pytest.skip('reference checkout not present')
-    with open(path) as f:
-        ref = yaml.safe_load(f)
+    assert GOLDEN[idx]['file'] == FILES[idx]
+    ref = GOLDEN[idx]['defaults']
+    assert ref
     for k, v in ref.items():
         assert k in cfg, (idx, k)
         if isinstance(v, float) or isinstance(cfg[k], float):
