@@ -34,6 +34,11 @@ SAC_DEFAULTS = dict(hidden_dim=256, activation='relu', norm_obs=False, norm_rewa
                     tau=0.005, init_temperature=0.2, use_entropy_tuning=False, target_entropy=None, train_interval=100,
                     train_batch_size=64, actor_lr=0.001, critic_lr=0.001, entropy_lr=0.001, warm_up_steps=1000,
                     max_buffer_size=1000000, **_RUNNER)                         # controllers/sac/sac.yaml
+# controllers/ddpg/ddpg.yaml
+DDPG_DEFAULTS = dict(hidden_dim=256, norm_obs=False, norm_reward=False, clip_obs=10., clip_reward=10., gamma=0.99, tau=0.005,
+                     random_process={'func': 'OrnsteinUhlenbeckProcess', 'std': {'func': 'LinearSchedule', 'args': 0.2}},
+                     train_interval=100, train_batch_size=64, actor_lr=0.001, critic_lr=0.001, warm_up_steps=10000,
+                     max_buffer_size=1000000, **_RUNNER)
 # controllers/rarl/rarl.yaml (its `pretrained`, `train_protagonist`, `train_adversary` keys are read by nothing upstream either)
 RARL_DEFAULTS = dict(PPO_DEFAULTS, agent_iterations=10, adversary_iterations=10, pretrained=None, train_protagonist=True,
                      train_adversary=True)
@@ -252,6 +257,38 @@ class SAC(HipController):
         self.impl.load(path, training=self.training)
 
 
+class DDPG(HipController):
+    """controllers/ddpg/ddpg.py:28-341."""
+    DEFAULTS = DDPG_DEFAULTS
+
+    def _build(self):
+        from safe_control_gym_amd import ddpg
+        self.activation = self.algo_config.setdefault('activation', 'relu')        # (ddpg.yaml has no such key: DDPGAgent's default)
+        dcfg = ddpg.DDPGConfig.from_dict(self.algo_config)
+        n = self.rollout_batch_size if self.training else self.eval_batch_size
+        self.env = self._vec(n, self.seed)
+        self.eval_env = None
+        self.impl = ddpg.DDPG(self.env, dcfg, seed=self.seed)
+        self._det = self.impl.agent.deterministic_policy()
+
+    def reset(self):
+        """ddpg.py:87-107: in training mode the noise process restarts from zero as well."""
+        super().reset()
+        if self.training:
+            self.impl.reset_noise()
+
+    def _act_module(self):
+        return self._det
+
+    def save(self, path, save_buffer=True):
+        """ddpg.py:116-141: agent, normalisers + (training) total_steps, obs, RNG state, env random state, noise process and, with
+        save_buffer (upstream's default: on), the replay ring."""
+        self.impl.save(path, training=self.training, save_buffer=save_buffer)
+
+    def load(self, path):
+        self.impl.load(path, training=self.training)
+
+
 class SafeExplorerPPO(PPO):
     """controllers/safe_explorer/safe_ppo.py:32-466 — two phases selected by the config, as upstream:
       pretraining: True    learn() = `constraint_epochs` x pretrain_step (random-action transitions -> constraint models); the
@@ -353,4 +390,4 @@ class SafeExplorerPPO(PPO):
         return hist
 
 
-# (the ids 'ppo', 'sac', 'rarl', 'rap', 'safe_explorer_ppo' are registered in registration.py with lazy entry points to these classes)
+# (the ids 'ppo', 'sac', 'ddpg', 'rarl', 'rap', 'safe_explorer_ppo' are registered in registration.py with lazy entry points to these classes)
