@@ -212,11 +212,26 @@ class PPO(HipController):
 
 
 class RARL(PPO):
-    """controllers/rarl/rarl.py."""
+    """controllers/rarl/rarl.py.  Extension key `fused_rollout=True` (not in RARL_DEFAULTS / RAP_DEFAULTS, which equal the YAML files):
+    the training env is built with the protagonist's shape and the adversaries (HipVecEnv(..., policy=, adversaries=)), so that the
+    collection runs as one scg_rollout_adversarial launch (rarl._TwoSided._collect_fused_both).  Evaluation keeps its own env."""
     DEFAULTS = RARL_DEFAULTS
 
     def _policy_shape(self):
         return None
+
+    def _n_adversaries(self):
+        return 1
+
+    def _build(self):
+        if not self.algo_config.get('fused_rollout'):
+            return super()._build()
+        from safe_control_gym_amd import ppo
+        pcfg = ppo.PPOConfig.from_dict(self.algo_config)
+        n = self.rollout_batch_size if self.training else self.eval_batch_size
+        self.env = self._vec(n, self.seed, (pcfg.hidden_dim, pcfg.activation), adversaries=self._n_adversaries())
+        self.eval_env = None
+        self.impl = self._make_impl(pcfg)
 
     def _make_impl(self, pcfg):
         from safe_control_gym_amd import rarl
@@ -227,6 +242,9 @@ class RARL(PPO):
 class RAP(RARL):
     """controllers/rarl/rap.py."""
     DEFAULTS = RAP_DEFAULTS
+
+    def _n_adversaries(self):
+        return int(self.num_adversaries)
 
     def _make_impl(self, pcfg):
         from safe_control_gym_amd import rarl

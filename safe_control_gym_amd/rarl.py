@@ -15,7 +15,14 @@ Both collectors are HIP-graph captured (static shapes): T x (protagonist step, a
 adversary channel, statistics) + both agents' bootstrap / GAE — one replay per collection.  RAP evaluates every member of
 the population on the whole batch and selects per env by index (population sizes are 2-4: rap.yaml:7), which keeps the
 shapes static while the groups are re-drawn every iteration.
+
+Fused collector (`_collect_fused_both`): on an env built with HipVecEnv(..., policy=(hidden, activation),
+adversaries=n) the T control steps of both sides are ONE scg_rollout_adversarial launch (both actors on the matrix cores inside
+the env kernel; RAP: each env's own adversary), followed by batched critic passes of both sides and both GAE passes — the same
+quantities as the PyTorch collector, captured in the same graph.
 """
+import warnings
+
 import time
 
 import numpy as np
@@ -47,6 +54,32 @@ class _TwoSided(PPO):
         self.v_adv = torch.zeros(self.T, self.N, **f)
         self.logp_adv = torch.zeros(self.T, self.N, **f)
         self._two_graph = None
+        self._fused_two_sided = False           # decided by the subclass once its adversaries exist (_setup_fused)
+
+    def _setup_fused(self, n_adversaries):
+        """The fused collector when the env carries the matching adversary shape, the library serves it, the protagonist has its flat
+        parameter vector and no running normaliser is on; an env that asked for adversaries it cannot get warns and keeps the PyTorch
+        collector."""
+        from safe_control_gym_amd import _adversarial
+        cfg, env = self.cfg, self.env
+        want = getattr(env, 'adversaries_requested', None)
+        if want is None:
+            return
+        shape = (cfg.hidden_dim, cfg.activation, int(n_adversaries))
+        ok = (getattr(env, 'adversary_shape', None) == shape and self.agent._flat is not None and not self._normalise
+              and _adversarial.supported(self.obs_dim, cfg.hidden_dim, self.act_dim, self.adv_dim, cfg.activation, int(n_adversaries)))
+        if not ok:
+            warnings.warn(f'{type(self).__name__}: no fused adversarial collector for env adversary shape '
+                          f'{getattr(env, "adversary_shape", None)} / wanted {shape} (normalisers: {self._normalise}); '
+                          'using the PyTorch collector', RuntimeWarning, stacklevel=3)
+            return
+        f = dict(device=self.device, dtype=torch.float32)
+        T, N = self.T, self.N
+        self._fused_two_sided = True
+        self._fv = (torch.zeros(T + 1, N, **f), torch.zeros(T + 1, N, **f))            # critic values of obs[0..T]: protagonist, adversary
+        self._ftv = (torch.zeros(T, N, **f), torch.zeros(T, N, **f))                    # ... of the terminal observations
+        self._f_episode_acc = torch.zeros(N, 8, **f)
+        self._f_adv_index = torch.zeros(N, dtype=torch.int32, device=self.device)
 
     def _adversary_step(self, obs):
         raise NotImplementedError
@@ -74,6 +107,80 @@ class _TwoSided(PPO):
             self.ep_length_sum += (out.fin_length * d).sum()
             self.ep_violation_sum += (out.fin_violation * d).sum()
 
+    # ---- fused collector ----------------------------------------------------------------------------------------
+    def _adversary_agents(self):
+        raise NotImplementedError
+
+    def _critic_rows(self, agent, x, out):
+        """out[m] = agent's critic(x[m]): the MFMA forward kernel (scg_mlp_forward, the protagonist's learner library — a critic's
+        shape does not depend on the action width) where the agent has a flat parameter vector, else the PyTorch critic."""
+        from safe_control_gym_amd import _learn
+        cfg = self.cfg
+        if agent._flat is not None and _learn.supported(self.obs_dim, cfg.hidden_dim, self.act_dim, cfg.activation):
+            import ctypes as C
+            D = _learn.lib(self.obs_dim, cfg.hidden_dim, self.act_dim, cfg.activation)
+            _, c_lay, _, _ = agent._layouts()
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            with torch.cuda.device(self.device):
+                _learn.check(D, D.scg_mlp_forward(agent._flat['p'].data_ptr(), C.byref(c_lay), 1, x.data_ptr(), int(x.shape[0]),
+                                                  out.data_ptr(), None, st))
+        else:
+            out.copy_(agent.ac.critic(x).squeeze(-1))
+
+    def _fused_values(self, side, agents):
+        """Critic values of obs[0..T] and of the terminal observations for one side; a population evaluates every member on all rows
+        and selects each env's own (static shapes)."""
+        T, N = self.T, self.N
+        v_all, tv = self._fv[side], self._ftv[side]
+        x, xt = self.obs.view((T + 1) * N, self.obs_dim), self.term_obs.view(T * N, self.obs_dim)
+        if len(agents) == 1:
+            self._critic_rows(agents[0], x, v_all.view(-1))
+            self._critic_rows(agents[0], xt, tv.view(-1))
+        else:
+            vs, ts = [], []
+            for a in agents:
+                vs.append(torch.empty((T + 1) * N, device=self.device))
+                ts.append(torch.empty(T * N, device=self.device))
+                self._critic_rows(a, x, vs[-1])
+                self._critic_rows(a, xt, ts[-1])
+            v_all.view(-1).copy_(self._select(vs))
+            tv.view(-1).copy_(self._select(ts))
+        return v_all, tv
+
+    def _fused_returns(self, v_all, tv, rew_buf):
+        """ppo_utils.py:374-402 on [T, N] buffers: time truncation bootstraps with the terminal observation's value (= _returns_body)."""
+        cfg, T = self.cfg, self.T
+        mask = 1.0 - self.done.to(torch.float32)
+        trunc = (self.flags & 1).bool() & self.done.bool()
+        terminal_v = torch.where(trunc, tv, torch.zeros_like(tv))
+        ret, adv = self._gae(rew_buf.clone(), v_all[:T].contiguous(), mask, terminal_v, v_all[T].contiguous(), cfg.gamma, cfg.gae_lambda,
+                             cfg.use_gae)
+        moments = torch.stack([adv.sum(), (adv * adv).sum(), torch.full((), float(adv.numel()), device=adv.device)])
+        return ret, adv, moments
+
+    @torch.no_grad()
+    def _collect_fused_both(self):
+        """One scg_rollout_adversarial launch for the T control steps of both sides, the batched critic passes of both sides, both
+        sides' bootstrap and GAE (the adversary's on -reward).  Device work only: _collect_both captures it in _two_graph."""
+        from safe_control_gym_amd import _adversarial
+        T = self.T
+        advs = self._adversary_agents()
+        n = len(advs)
+        if n > 1:
+            self._f_adv_index.copy_(self.adv_index)
+        self.env.rollout_adversarial(self._policy_struct(), [_adversarial.actor_ptrs(a.ac.actor) for a in advs], T, self.obs, self.act,
+                                     self.logp, self.rew, self.done, self.flags, self.act_adv, self.logp_adv,
+                                     adv_index=self._f_adv_index if n > 1 else None, terminal_obs=self.term_obs,
+                                     episode_acc=self._f_episode_acc)
+        # finished episodes (count, return, length, violation steps) of this collection, once
+        self._ep_tot += self._f_episode_acc[:, :4].sum(0)
+        self._f_episode_acc.zero_()
+        v_all, tv = self._fused_values(0, [self.agent])
+        self.v.copy_(v_all[:T])
+        va_all, tva = self._fused_values(1, advs)
+        self.v_adv.copy_(va_all[:T])
+        return self._fused_returns(v_all, tv, self.rew), self._fused_returns(va_all, tva, -self.rew)
+
     def _both_returns(self, dense):
         ag = self._returns_body(dense)
         ad = self._returns_body(dense, self._adversary_critic, -self.rew, self.v_adv)
@@ -81,7 +188,9 @@ class _TwoSided(PPO):
 
     def _collect_both(self):
         """One collection + the (returns, advantages, moments) of both sides; a graph replay when graphs are on."""
-        if self._graph_rollout:
+        if self._fused_two_sided:
+            res = self._collect_fused_two_graph()
+        elif self._graph_rollout:
             epoch = getattr(self.env, 'seed_epoch', 0)
             if self._two_graph is None or self._two_graph[2] != epoch:
                 dev = self.device
@@ -107,6 +216,25 @@ class _TwoSided(PPO):
         self.total_steps += self.T * self.N * parallel.world_size()
         return res
 
+    def _collect_fused_two_graph(self):
+        """The fused collection: eagerly the first time after a (re)seed (libraries load, kernel attributes are set), captured the
+        second time, replayed from then on; eagerly every time without graphs."""
+        if not self._graph_rollout:
+            return self._collect_fused_both()
+        epoch = getattr(self.env, 'seed_epoch', 0)
+        st = self._two_graph
+        if st is None or st[2] != epoch:
+            self._two_graph = (None, None, epoch)
+            return self._collect_fused_both()
+        if st[0] is None:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode='thread_local'):
+                out = self._collect_fused_both()
+            self._two_graph = st = (g, out, epoch)
+        st[0].replay()
+        (r0, a0, m0), (r1, a1, m1) = st[1]
+        return (r0, a0, m0.clone()), (r1, a1, m1.clone())
+
     def _data(self, adversary, ret, adv, lo=0, hi=None):
         hi = self.N if hi is None else hi
         n = hi - lo
@@ -123,6 +251,10 @@ class RARL(_TwoSided):
         super().__init__(env, cfg, seed)
         self.agent_iterations, self.adversary_iterations = int(agent_iterations), int(adversary_iterations)
         self.adversary = PPOAgent(self.obs_dim, self.adv_dim, cfg, self.device)
+        self._setup_fused(1)
+
+    def _adversary_agents(self):
+        return [self.adversary]
 
     def _adversary_step(self, obs):
         return self.adversary.ac.step(obs)
@@ -167,6 +299,10 @@ class RAP(_TwoSided):
         self._rng = np.random.RandomState(seed)               # rap.py:356 draws from NumPy's global stream
         self.adv_index = torch.zeros(self.N, dtype=torch.long, device=self.device)
         self.groups = []
+        self._setup_fused(self.num_adversaries)
+
+    def _adversary_agents(self):
+        return self.adversaries
 
     def _select(self, per_adv):
         """per_adv: list (one per adversary) of [N, ...] tensors (or [T*N, ...], time-major) -> rows of each env's adversary."""

@@ -200,7 +200,7 @@ class HipVecEnv(VecEnv):
     """N independent copies of one environment stepped by libscg_hip.so on one GPU."""
 
     def __init__(self, env_id, num_envs, seed=0, device=None, dtype=torch.float32, env_id_offset=0,
-                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, **task_config):
+                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, **task_config):
         L.lib()                                        # fail loudly, before touching torch.cuda
         if not torch.cuda.is_available():
             raise L.ScgError('HipVecEnv needs a HIP device (torch.cuda.is_available() is False); '
@@ -231,7 +231,22 @@ class HipVecEnv(VecEnv):
         if policy is not None and dtype == torch.float32 and L.policy_supported(self.spec.obs_dim, int(policy[0]), self.spec.nu, policy[1]) \
                 and self.spec.obs_dim in (self.spec.nx, 2 * self.spec.nx):
             self.policy_shape = (int(policy[0]), policy[1])
-        self._lib, self.specialized = L.lib_for(cfg, specialize, self.policy_shape)
+        # adversaries=n (with policy=): the library that also carries the RARL / RAP collector (rollout_adversarial below) for the
+        # protagonist's shape and n adversaries of the same shape; a shape it cannot serve leaves adversary_shape None
+        self.adversary_shape = None
+        self.adversaries_requested = None
+        if adversaries is not None:
+            if spec.adversary_disturbance is None:
+                raise ValueError('adversaries= needs a task config with adversary_disturbance set')
+            from safe_control_gym_amd import _adversarial
+            self.adversaries_requested = int(adversaries)
+            if self.policy_shape is not None and _adversarial.supported(spec.obs_dim, self.policy_shape[0], spec.nu, spec.adversary_dim,
+                                                                        self.policy_shape[1], self.adversaries_requested):
+                self.adversary_shape = self.policy_shape + (self.adversaries_requested,)
+        if self.adversary_shape is not None:
+            self._lib, self.specialized = _adversarial.lib_for(cfg, *self.adversary_shape), True
+        else:
+            self._lib, self.specialized = L.lib_for(cfg, specialize, self.policy_shape)
         self._cfg = cfg
         nbytes = C.c_size_t(0)
         self._chk(self._lib.scg_workspace_bytes(C.byref(cfg), C.byref(nbytes)))
@@ -383,6 +398,28 @@ class HipVecEnv(VecEnv):
         o.max_episodes = int(max_episodes)
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_policy(self._h, C.byref(policy), int(k_steps), C.byref(o), self._stream()))
+
+    def rollout_adversarial(self, policy, adversaries, k_steps, obs, act, logp, reward, done, flags, adv_act, adv_logp, adv_index=None,
+                            deterministic_adversary=False, terminal_obs=None, episode_acc=None, max_episodes=0):
+        """K control steps in ONE launch with the protagonist AND the adversary (or, with a population, each env's adversary) in the
+        loop (scg_rollout_adversarial): `policy` is the protagonist's _lib.Policy, `adversaries` a list of _adversarial.ActorPtrs,
+        adv_index an int32 [N] device tensor (population only); adv_act [K, N, adv_dim] / adv_logp [K, N] receive the raw sampled
+        adversary actions and their log-probabilities, the other arguments are as for rollout_policy."""
+        from safe_control_gym_amd import _adversarial
+        if self.adversary_shape is None:
+            raise L.ScgError('this env was not built with an adversary shape (HipVecEnv(..., policy=(hidden, activation), adversaries=n))')
+        if adv_index is not None and (adv_index.dtype != torch.int32 or adv_index.numel() != self.num_envs or not adv_index.is_contiguous()):
+            raise ValueError(f'adv_index must be a contiguous int32 tensor of {self.num_envs} entries')
+        o = L.PolicyRollout()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        o.d_obs, o.d_act, o.d_logp, o.d_reward, o.d_done, o.d_flags = p(obs), p(act), p(logp), p(reward), p(done), p(flags)
+        o.d_terminal_obs, o.d_ep_stats, o.d_episode_acc = p(terminal_obs), p(self.ep_stats), p(episode_acc)
+        o.max_episodes = int(max_episodes)
+        arr = (_adversarial.ActorPtrs * len(adversaries))(*adversaries)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_adversarial(self._h, C.byref(policy), arr, len(adversaries), p(adv_index),
+                                                        int(bool(deterministic_adversary)), int(k_steps), C.byref(o), p(adv_act),
+                                                        p(adv_logp), self._stream()))
 
     def step_sequence(self, actions, adv_actions=None, out=None, terminal_obs=True, mse=False, c_values=False, fin_stats=False,
                       state=False, noisy_action=False):
