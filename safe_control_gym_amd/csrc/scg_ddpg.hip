@@ -578,7 +578,7 @@ __global__ __launch_bounds__(256) void ring_push_kernel(const RingArgs R, float*
     R.obs[slot * NOBS + e] = cur_obs[gid];
     R.next_obs[slot * NOBS + e] = trunc ? term[gid] : nv;
     cur_obs[gid] = nv;
-    if (e < NU) R.act[slot * NU + e] = act[(size_t)i * NU + e];
+    for (int j = e; j < NU; j += NOBS) R.act[slot * NU + j] = act[(size_t)i * NU + j];     // every action column, also when NOBS < NU
     if (e == 0) { R.rew[slot] = rew[i]; R.mask[slot] = trunc ? 1.0f : (dn ? 0.0f : 1.0f); }
 }
 struct CommitArgs { double* x_prev; const double* x_next; int64_t* calls; int32_t* pending; int kind; };
