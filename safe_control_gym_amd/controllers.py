@@ -312,11 +312,39 @@ class SafeExplorerPPO(PPO):
       pretraining: True    learn() = `constraint_epochs` x pretrain_step (random-action transitions -> constraint models); the
                            checkpoint's 'safety_layer' is what the second phase loads;
       pretraining: False   reset() loads the safety layer from `pretrained` (a checkpoint file, or a directory holding
-                           model_latest.pt; safe_ppo.py:96-100) and learn() is PPO with the safety-filtered policy."""
+                           model_latest.pt; safe_ppo.py:96-100) and learn() is PPO with the safety-filtered policy.
+    Extension key `fused_rollout=True` (not in SAFE_EXPLORER_PPO_DEFAULTS, which equal the YAML): the training and evaluation envs are
+    built with the actor's and the safety layer's shape (HipVecEnv(..., policy=(hidden_dim, activation), safety_layer=
+    constraint_hidden_dim)), so that the PPO phase collects with one scg_rollout_safe launch and run() evaluates with one.  An
+    unservable shape, a safety layer of more than one hidden layer or a running normaliser warns and keeps the eager path; the
+    pre-training phase always runs eagerly (random actions, not the policy)."""
     DEFAULTS = SAFE_EXPLORER_PPO_DEFAULTS
 
+    def _safety_shape(self):
+        """(policy, safety_layer) arguments of the envs: the fused collector's shape when asked for and servable, else (None, None)."""
+        from safe_control_gym_amd import _safe_explorer
+        from safe_control_gym_amd.env_config import EnvSpec
+        if not self.algo_config.get('fused_rollout') or self.norm_obs or self.norm_reward:
+            return None, None
+        hc = self.constraint_hidden_dim
+        if isinstance(hc, (list, tuple)):
+            if len(hc) != 1:
+                return None, None
+            hc = hc[0]
+        spec = EnvSpec(self.env_id, dict(self.task_config))
+        if spec.obs_dim not in (spec.nx, 2 * spec.nx) or not _safe_explorer.supported(spec.obs_dim, self.hidden_dim, spec.nu, self.activation,
+                                                                                      spec.n_state_con_rows, hc):
+            return None, None
+        return (self.hidden_dim, self.activation), int(hc)
+
+    def _vec(self, n, seed, policy=None, **over):
+        pol, hc = self._safety_shape()
+        if hc is None:
+            return super()._vec(n, seed, policy, **over)
+        return super()._vec(n, seed, pol, safety_layer=hc, **over)
+
     def _policy_shape(self):
-        return None                                 # the safety layer sits inside the actor: no fused collector
+        return None                                 # (the fused collector's shape comes with safety_layer=, _vec above)
 
     def _build(self):
         self.activation = self.algo_config.setdefault('activation', 'tanh')         # (safe_ppo_utils.py: the PPO networks' default)

@@ -11,8 +11,14 @@ Mirrors /root/reference/safe_control_gym/controllers/safe_explorer/:
 What the env kernel provides: `c_values` of every step (pre-reset values where the episode ended — exactly upstream's
 `terminal_info['constraint_values']`); the constraint values of a freshly reset env are evaluated from the returned state
 by `EnvSpec.state_constraint_values`.
+
+Fused collector (opt-in with cfg.extra['fused_rollout']): on an env built with HipVecEnv(..., policy=(hidden, activation),
+safety_layer=Hc) the T control steps — actor mean, safety-layer projection, sampling, env step and the next step's constraint values —
+are ONE scg_rollout_safe launch, followed by one batched critic pass and the usual bootstrap / GAE.  `evaluate` runs the deterministic
+kernel on an evaluation env that carries the same shape.  Unservable shapes and running normalisers warn and keep the eager path.
 """
 import time
+import warnings
 
 import torch
 import torch.nn as nn
@@ -115,6 +121,60 @@ class SafeExplorerPPO(PPO):
                                         terminal_obs=self.term_obs[t], noisy_action=None, mse=None) for t in range(self.T)]
         self.obs[0].copy_(self.obs_normalizer(env.reset_tensors()))
         self.c = self._reset_c(env.out)
+        self._setup_fused(constraint_hidden_dim)
+
+    def _setup_fused(self, hidden_c):
+        """The fused collector when cfg.extra['fused_rollout'] is set, the env carries the matching (hidden, activation, Hc) shape and
+        no running normaliser is on; otherwise (when asked for) a warning and the eager collector."""
+        from safe_control_gym_amd import _safe_explorer
+        self._fused_safe = None
+        if not self.cfg.extra.get('fused_rollout'):
+            return
+        hc = hidden_c[0] if isinstance(hidden_c, (list, tuple)) and len(hidden_c) == 1 else hidden_c
+        shape = (self.cfg.hidden_dim, self.cfg.activation, hc) if isinstance(hc, int) else None
+        ok = (shape is not None and getattr(self.env, 'safety_shape', None) == shape and not self._normalise
+              and _safe_explorer.supported(self.obs_dim, self.cfg.hidden_dim, self.act_dim, self.cfg.activation, self.C, hc))
+        if not ok:
+            warnings.warn(f'SafeExplorerPPO: no fused collector for env shape {getattr(self.env, "safety_shape", None)} / wanted '
+                          f'{(self.cfg.hidden_dim, self.cfg.activation, hidden_c)} (normalisers: {bool(self._normalise)}); using the eager '
+                          'collector', RuntimeWarning, stacklevel=3)
+            return
+        self._fused_safe = shape
+        self._f_episode_acc = torch.zeros(self.N, 8, device=self.device)
+        self._safety_packed = None
+        self._safety_version = None
+
+    def _packed_safety(self):
+        """The packed safety layer (_safe_explorer.pack_safety_layer), re-packed whenever a parameter of the layer has changed since."""
+        from safe_control_gym_amd import _safe_explorer
+        params = list(self.safety_layer.constraint_models.parameters())
+        version = tuple((p.data_ptr(), p._version) for p in params)
+        if self._safety_packed is None or version != self._safety_version:
+            self._safety_packed = _safe_explorer.pack_safety_layer(self.safety_layer.constraint_models, self.obs_dim, self.act_dim,
+                                                                   self._fused_safe[2])
+            self._safety_version = version
+        return self._safety_packed
+
+    def _carry(self):
+        """self.c as the kernel's in/out carry: a contiguous float32 [N, C] tensor on the env device."""
+        if self.c.dtype != torch.float32 or not self.c.is_contiguous() or self.c.device != self.device:
+            self.c = self.c.to(self.device, torch.float32).contiguous()
+        return self.c
+
+    @torch.no_grad()
+    def _collect_fused(self, count_steps=True):
+        """One scg_rollout_safe launch for the T control steps (obs / act / logp / rew / done / flags / term_obs / c_buf, self.c carried),
+        then one batched critic pass for the values; the bootstrap and GAE follow in _returns_body."""
+        from safe_control_gym_amd import _adversarial
+        T, N = self.T, self.N
+        self.env.rollout_safe(_adversarial.actor_ptrs(self.agent.ac.actor), self._packed_safety(), self.safety_layer.slack, T, self.obs,
+                              self.act, self.logp, self.rew, self.done, self.flags, self.c_buf, self._carry(), terminal_obs=self.term_obs,
+                              episode_acc=self._f_episode_acc)
+        self._ep_tot += self._f_episode_acc[:, :4].sum(0)
+        self._f_episode_acc.zero_()
+        self.v.copy_(self.agent.ac.critic(self.obs[:T].reshape(T * N, self.obs_dim)).reshape(T, N))
+        if count_steps:
+            self.total_steps += T * N * parallel.world_size()
 
     def _reset_c(self, out, env=None):
         return (env or self.env).spec.state_constraint_values(out.state.t()).to(torch.float32)
@@ -177,6 +237,8 @@ class SafeExplorerPPO(PPO):
         """SafeExplorerPPO.run (safe_ppo.py:230-279) batched: the deterministic, safety-filtered policy on every env of `env` with
         the constraint values of the current state as its second input; per-env totals of the first `episodes_per_env` episodes."""
         N, dev = env.num_envs, env.device
+        if self._fused_safe is not None and getattr(env, 'safety_shape', None) == self._fused_safe:
+            return self._evaluate_fused(env, episodes_per_env)
         acc = {k: torch.zeros(N, device=dev) for k in ('count', 'ret', 'length', 'viol', 'mse')}
         nz = self.obs_normalizer
         frozen = nz.read_only
@@ -195,6 +257,30 @@ class SafeExplorerPPO(PPO):
             obs = nz(out.obs)
         nz.read_only = frozen
         return acc
+
+    @torch.no_grad()
+    def _evaluate_fused(self, env, episodes_per_env=1):
+        """evaluate() as ONE scg_rollout_safe launch with the filtered mean (deterministic=1); per-env totals of the first
+        `episodes_per_env` episodes accumulated in the kernel."""
+        from safe_control_gym_amd import _adversarial
+        N, dev = env.num_envs, env.device
+        steps = env.spec.max_episode_steps * episodes_per_env
+        buf = getattr(env, '_eval_safe', None)
+        if buf is None or buf['rew'].shape[0] != steps:
+            f = dict(device=dev, dtype=torch.float32)
+            u8 = dict(device=dev, dtype=torch.uint8)
+            buf = {'obs': torch.zeros(steps + 1, N, self.obs_dim, **f), 'act': torch.zeros(steps, N, self.act_dim, **f),
+                   'logp': torch.zeros(steps, N, **f), 'rew': torch.zeros(steps, N, **f), 'done': torch.zeros(steps, N, **u8),
+                   'flags': torch.zeros(steps, N, **u8), 'c_rows': torch.zeros(steps, N, self.C, **f), 'acc': torch.zeros(N, 8, **f)}
+            env._eval_safe = buf
+        env.reset_tensors()
+        carry = self._reset_c(env.out, env).contiguous()
+        buf['acc'].zero_()
+        env.rollout_safe(_adversarial.actor_ptrs(self.agent.ac.actor), self._packed_safety(), self.safety_layer.slack, steps, buf['obs'],
+                         buf['act'], buf['logp'], buf['rew'], buf['done'], buf['flags'], buf['c_rows'], carry, deterministic=True,
+                         episode_acc=buf['acc'], max_episodes=episodes_per_env)
+        a = buf['acc']
+        return {'count': a[:, 0], 'ret': a[:, 1], 'length': a[:, 2], 'viol': a[:, 3], 'mse': a[:, 4]}
 
     # ---- checkpoints with upstream's keys (safe_ppo.py:146-176): agent, safety_layer, normalisers
     def checkpoint_state(self, training=True):
@@ -263,7 +349,10 @@ class SafeExplorerPPO(PPO):
 
     def train_step(self):
         t0 = time.perf_counter()
-        self.collect()
+        if self._fused_safe is not None:
+            self._collect_fused()
+        else:
+            self.collect()
         ret, adv, moments = self._returns_body(dense=False)
         with torch.no_grad():
             parallel.all_reduce_sum_(moments)

@@ -200,7 +200,7 @@ class HipVecEnv(VecEnv):
     """N independent copies of one environment stepped by libscg_hip.so on one GPU."""
 
     def __init__(self, env_id, num_envs, seed=0, device=None, dtype=torch.float32, env_id_offset=0,
-                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, **task_config):
+                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, safety_layer=None, **task_config):
         L.lib()                                        # fail loudly, before touching torch.cuda
         if not torch.cuda.is_available():
             raise L.ScgError('HipVecEnv needs a HIP device (torch.cuda.is_available() is False); '
@@ -243,8 +243,23 @@ class HipVecEnv(VecEnv):
             if self.policy_shape is not None and _adversarial.supported(spec.obs_dim, self.policy_shape[0], spec.nu, spec.adversary_dim,
                                                                         self.policy_shape[1], self.adversaries_requested):
                 self.adversary_shape = self.policy_shape + (self.adversaries_requested,)
+        # safety_layer=Hc (with policy=): the library that also carries the Safe-Explorer PPO collector (rollout_safe below) for the
+        # actor's shape and a one-hidden-layer safety layer of Hc units per state constraint; a shape it cannot serve leaves
+        # safety_shape None
+        self.safety_shape = None
+        self.safety_requested = None
+        if safety_layer is not None and adversaries is None:
+            from safe_control_gym_amd import _safe_explorer
+            self.safety_requested = safety_layer
+            if self.policy_shape is not None and _safe_explorer.supported(spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1],
+                                                                         spec.n_state_con_rows, safety_layer):
+                hc = safety_layer[0] if isinstance(safety_layer, (list, tuple)) else safety_layer
+                self.safety_shape = self.policy_shape + (int(hc),)
         if self.adversary_shape is not None:
             self._lib, self.specialized = _adversarial.lib_for(cfg, *self.adversary_shape), True
+        elif self.safety_shape is not None:
+            from safe_control_gym_amd import _safe_explorer
+            self._lib, self.specialized = _safe_explorer.lib_for(cfg, *self.safety_shape), True
         else:
             self._lib, self.specialized = L.lib_for(cfg, specialize, self.policy_shape)
         self._cfg = cfg
@@ -420,6 +435,34 @@ class HipVecEnv(VecEnv):
             self._chk(self._lib.scg_rollout_adversarial(self._h, C.byref(policy), arr, len(adversaries), p(adv_index),
                                                         int(bool(deterministic_adversary)), int(k_steps), C.byref(o), p(adv_act),
                                                         p(adv_logp), self._stream()))
+
+    def rollout_safe(self, actor, safety, slack, k_steps, obs, act, logp, reward, done, flags, c_rows, c_carry, deterministic=False,
+                     terminal_obs=None, episode_acc=None, max_episodes=0):
+        """K control steps of Safe-Explorer PPO in ONE launch (scg_rollout_safe): actor mean, safety-layer projection, sample, env step
+        and the next step's constraint values.  `actor` is an _adversarial.ActorPtrs, `safety` the packed float32 layer
+        (_safe_explorer.pack_safety_layer), `slack` float32 [C]; c_rows [K, N, C] receives the constraint values each step's policy saw,
+        c_carry [N, C] holds those of the current state (read, then overwritten with those after the last step); the other arguments
+        are as for rollout_policy."""
+        if self.safety_shape is None:
+            raise L.ScgError('this env was not built with a safety-layer shape (HipVecEnv(..., policy=(hidden, activation), safety_layer=Hc))')
+        C_ = self.spec.n_state_con_rows
+        if c_rows.shape != (int(k_steps), self.num_envs, C_) or c_carry.shape != (self.num_envs, C_):
+            raise ValueError(f'c_rows must be [{int(k_steps)}, {self.num_envs}, {C_}] and c_carry [{self.num_envs}, {C_}]')
+        from safe_control_gym_amd import _safe_explorer
+        if safety.numel() != _safe_explorer.packed_words(self.spec.obs_dim, self.spec.nu, C_, self.safety_shape[2]) or slack.numel() != C_:
+            raise ValueError('safety must be the packed layer of this shape (_safe_explorer.pack_safety_layer) and slack hold one value '
+                             'per state constraint')
+        for t in (safety, slack, c_rows, c_carry):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('safety, slack, c_rows and c_carry must be contiguous float32 tensors on the env device')
+        o = L.PolicyRollout()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        o.d_obs, o.d_act, o.d_logp, o.d_reward, o.d_done, o.d_flags = p(obs), p(act), p(logp), p(reward), p(done), p(flags)
+        o.d_terminal_obs, o.d_ep_stats, o.d_episode_acc = p(terminal_obs), p(self.ep_stats), p(episode_acc)
+        o.max_episodes = int(max_episodes)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_safe(self._h, C.byref(actor), p(safety), p(slack), int(bool(deterministic)), int(k_steps),
+                                                 C.byref(o), p(c_rows), p(c_carry), self._stream()))
 
     def step_sequence(self, actions, adv_actions=None, out=None, terminal_obs=True, mse=False, c_values=False, fin_stats=False,
                       state=False, noisy_action=False):
