@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""bench.py — the whole BASELINE.json metric in one JSON line: env-steps/s of the HIP simulator on the headline config
-+ PPO wall-clock-to-reward on it, with the per-kernel roofline and the CPU path timed beside it.
+"""bench.py — env-steps/s of the HIP simulator on the headline config in one JSON line; with --full the whole BASELINE.json
+metric: + PPO wall-clock-to-reward on it, with the per-kernel roofline and the CPU path timed beside it.
 
 Headline (the top-level fields): Quadrotor2D trajectory tracking (BASELINE configs[2]; examples/rl/config_overrides/
 quadrotor_2D/quadrotor_2D_track.yaml), 65 536 envs per GPU, float32.  One "step" = one control step of every env = ONE
@@ -10,7 +10,10 @@ benchmark is the same open-loop random-action loop on one env).  Exactly K = --s
 barrier + synchronize, as replays of HIP graphs of up to --graph-len steps; `ms_per_step` is that region / K.
 `--dump-outputs DIR` writes what the last timed step returned to its caller (obs, reward, done, ... of every env; a fixed
 seeded sample of envs when that exceeds 64 MB) as DIR/<name>.npy; inputs are seeded, so two builds compare output for output.
+A plain run does only that: set-up, warm-up, the K timed steps, the dump, the line.
 
+`--full` adds everything else, each part after the timed steps: `roofline` (the launch period of >= 4000 more back-to-back
+steps) and `config.finite_outputs`, then the secondary objects and the CPU baseline below.
 Secondary objects (rank 0, N = 1): `f64` (the float64 kernels of the same workload), `secondary` (the other BASELINE
 configs' env kernels: cartpole_stab incl. the fused random-action rollout of config #2, quadrotor_3D_track[_disturbed]),
 `gae` (scg_gae timing + its own roofline), `sequence` (scg_step_sequence: K control steps per launch, the mode that carries >= 0.40 of the
@@ -74,8 +77,12 @@ def parse():
     ap.add_argument('--task', default='quadrotor_2D_track')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'f64'])
     ap.add_argument('--no-graph', action='store_true', help='launch every step from Python instead of a HIP graph')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure the roofline, check the outputs and run the other legs (f64, other configs, '
+                         'gae, sequence, fused rollout, ppo, sac, multi-GPU probe, CPU baseline); --no-secondary, --no-cpu-baseline, '
+                         '--cpu-seconds, --ppo-* and --sac-* shape those')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='headline only (no f64 / other configs / gae / ppo legs)')
+    ap.add_argument('--no-secondary', action='store_true', help='headline and roofline only (no f64 / other configs / gae / ppo legs)')
     ap.add_argument('--generic', action='store_true', help='use libscg_hip.so (any config, parameters via LDS) instead of the config-specialised build')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='budget of the CPU oracle baseline')
     ap.add_argument('--graph-len', type=int, default=1000, help='steps captured per HIP graph')
@@ -1099,8 +1106,6 @@ def main():
     elapsed = float(el.item())
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, hb.outputs(), N)      # what the last timed step left, before any further step
-    period_us = hb.kernel_period_us(max(args.steps, 4000))      # launch period inside long back-to-back replays
-    ok = hb.sane()
     value = world * N * done_steps / elapsed
     out = None
     if rank == 0:
@@ -1115,15 +1120,26 @@ def main():
                                    f'{"HIP graph of %d steps" % G if hb.graph is not None else "per-step Python launches"}',
                        'envs_per_gpu': N, 'task_yaml': f'safe_control_gym_amd/configs/{args.task}.yaml',
                        'parallelism': f'env-shard x{world}', 'rccl_ranks': rccl_ranks, 'collective_backend': backend if world > 1 else None,
-                       'finite_outputs': ok,
                        'kernel_build': 'config-specialised' if hb.env.specialized else 'generic',
                        'timing': f'one timed region of {done_steps} steps'
                                  + ('; per rank: barrier + synchronize, clock, K steps, synchronize, clock, barrier; MAX over ranks' if world > 1 else ''),
                        'timed_region_ms': round(1e3 * elapsed, 4)},
-            'roofline': roofline_of(args.task, args.dtype, N, period_us, driver_step_us=1e6 * elapsed / done_steps,
-                                    geometry=launch_geometry(N, bool(hb.env.specialized), args.task)),
         }
-    full = not args.no_secondary and args.task == 'quadrotor_2D_track' and args.dtype == 'f32'
+    if not args.full:
+        # a plain run: the headline and nothing else
+        hb.env.close()
+        if rank == 0:
+            print(json.dumps(out, default=str))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    period_us = hb.kernel_period_us(max(args.steps, 4000))      # launch period inside long back-to-back replays
+    ok = hb.sane()
+    if rank == 0:
+        out['config']['finite_outputs'] = ok
+        out['roofline'] = roofline_of(args.task, args.dtype, N, period_us, driver_step_us=1e6 * elapsed / done_steps,
+                                      geometry=launch_geometry(N, bool(hb.env.specialized), args.task))
+    legs = not args.no_secondary and args.task == 'quadrotor_2D_track' and args.dtype == 'f32'
     # The learning legs run collectives (N > 1: RCCL).  A rank that dies or hangs inside one must not cost the run its line:
     # after a generous limit every rank gives up, rank 0 prints what it has (the headline is complete at this point).
     import threading
@@ -1139,7 +1155,7 @@ def main():
     watchdog.daemon = True
     if world > 1:
         watchdog.start()
-    if rank == 0 and world == 1 and full:
+    if rank == 0 and world == 1 and legs:
         try:
             fb = StepBench(torch, args.task, N, torch.float64, graph_len=500)
             fb.do(500)
@@ -1166,7 +1182,7 @@ def main():
         except Exception as exc:                                    # noqa: BLE001
             out['fused_rollout'] = {'error': repr(exc)[:200]}
     hb.env.close()
-    if full and args.ppo_seeds > 0 and (world == 1 or backend == 'nccl' or os.environ.get('SCG_BENCH_PPO_GLOO')):
+    if legs and args.ppo_seeds > 0 and (world == 1 or backend == 'nccl' or os.environ.get('SCG_BENCH_PPO_GLOO')):
         try:
             res = ppo_leg(torch, dist, world, rank, args.ppo_seeds, args.ppo_seconds, envs=args.ppo_envs)
             if world == 1 and args.ppo_envs != 16384:           # the small-batch point (round 2's leg) under the same protocol and target
@@ -1185,7 +1201,7 @@ def main():
             res = {'error': repr(exc)[:300], 'trace': traceback.format_exc()[-600:]}
         if rank == 0:
             out['ppo'] = res
-    if full and args.sac_seeds > 0 and (world == 1 or backend == 'nccl' or os.environ.get('SCG_BENCH_SAC_GLOO')):
+    if legs and args.sac_seeds > 0 and (world == 1 or backend == 'nccl' or os.environ.get('SCG_BENCH_SAC_GLOO')):
         try:
             res = sac_leg(torch, args.sac_seeds, args.sac_seconds, world=world, rank=rank)
             if world == 1:          # config #5 WITH parameter disturbances (flyable additive deltas), target re-measured under them
@@ -1196,14 +1212,14 @@ def main():
         if rank == 0:
             out['sac'] = res
     probe = None
-    if full and world > 1 and backend == 'nccl':            # every rank: the all-reduce of the learners' buckets on the REAL group
+    if legs and world > 1 and backend == 'nccl':            # every rank: the all-reduce of the learners' buckets on the REAL group
         try:
             from safe_control_gym_amd import parallel
             probe = parallel.allreduce_probe((4 * 36742, 4 * 61451))
         except Exception as exc:                                    # noqa: BLE001
             probe = {'error': repr(exc)[:300]}
     watchdog.cancel()
-    if rank == 0 and full:
+    if rank == 0 and legs:
         out['multi_gpu'] = multi_gpu_readiness(torch, dist, world)
         if probe is not None:
             probe['note'] = f'{world} ranks over RCCL, in-place fp32 SUM, microseconds per collective (eager; 50 per HIP-graph replay)'

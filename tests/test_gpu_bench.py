@@ -1,5 +1,5 @@
 """bench.py on one GPU: --steps is the number of timed steps (also when it is not a multiple of --graph-len), and --dump-outputs
-writes the last timed step's outputs, identical from run to run."""
+writes the last timed step's outputs, identical from run to run and with or without --full."""
 import json
 import os
 import subprocess
@@ -12,9 +12,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(dump, steps, graph_len, envs=4096):
+def _bench(dump, steps, graph_len, envs=4096, extra=('--full', '--no-secondary', '--no-cpu-baseline')):
     cmd = [sys.executable, 'bench.py', '--gpus', '1', '--steps', str(steps), '--warmup', '7', '--graph-len', str(graph_len),
-           '--envs', str(envs), '--no-secondary', '--no-cpu-baseline', '--dump-outputs', str(dump)]
+           '--envs', str(envs), *extra, '--dump-outputs', str(dump)]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
@@ -39,3 +39,22 @@ def test_bench_times_exactly_steps_and_dumps_the_same_outputs_twice(tmp_path):
     # a different number of steps leaves different outputs: the dump is the state after the timed steps, not after set-up
     _bench(tmp_path / 'c', 1499, 1000, envs)
     assert not np.array_equal(np.load(tmp_path / 'a' / 'obs.npy'), np.load(tmp_path / 'c' / 'obs.npy'))
+
+
+def test_plain_bench_is_the_headline_alone_and_dumps_what_full_dumps(tmp_path):
+    """Without --full the line is the headline alone, whatever the other options ask for (no roofline, output check, legs or CPU
+    baseline), and the dumped outputs are those of a --full run: what --full adds runs after the dump."""
+    envs = 4096
+    full = _bench(tmp_path / 'full', 1200, 500, envs)
+    plain = _bench(tmp_path / 'plain', 1200, 500, envs, extra=())
+    assert set(plain) == {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                          'vs_baseline', 'dtype', 'data', 'config'}
+    assert set(full) - set(plain) == {'roofline'} and set(full['config']) - set(plain['config']) == {'finite_outputs'}
+    for k in ('metric', 'unit', 'n_gpus', 'steps', 'warmup', 'higher_is_better', 'dtype'):
+        assert plain[k] == full[k], k
+    assert plain['steps'] == 1200 and plain['ms_per_step'] > 0
+    assert plain['value'] == pytest.approx(envs * 1200 / (plain['ms_per_step'] * 1e-3 * 1200), rel=1e-9)
+    names = sorted(os.listdir(tmp_path / 'full'))
+    assert names == sorted(os.listdir(tmp_path / 'plain')) and 'obs.npy' in names
+    for f in names:
+        np.testing.assert_array_equal(np.load(tmp_path / 'plain' / f), np.load(tmp_path / 'full' / f), err_msg=f)

@@ -32,7 +32,7 @@ def _torchrun(script_args, extra_env, timeout=600, nproc=2):
 
 
 def test_bench_two_ranks_on_one_gpu():
-    out = _torchrun(['bench.py', '--gpus', '2', '--steps', '500', '--warmup', '100', '--no-secondary'], {'SCG_BENCH_BACKEND': 'gloo'})
+    out = _torchrun(['bench.py', '--gpus', '2', '--steps', '500', '--warmup', '100', '--full', '--no-secondary'], {'SCG_BENCH_BACKEND': 'gloo'})
     lines = [l for l in out.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out                     # rank 0 only
     r = json.loads(lines[0])
@@ -73,8 +73,8 @@ def test_plain_python_bench_gpus_2_spawns_its_own_ranks_and_mismatches_fail():
 def test_bench_ppo_leg_two_ranks_on_one_gpu():
     """The PPO wall-clock leg of bench.py with two ranks (what the driver's N > 1 runs execute over RCCL): env shards, one
     flat gradient all-reduce per minibatch, asynchronous evaluation per rank, rank 0's stop flag broadcast every iteration."""
-    out = _torchrun(['bench.py', '--gpus', '2', '--steps', '200', '--warmup', '50', '--ppo-seeds', '1', '--ppo-seconds', '3', '--ppo-envs', '16384'],
-                    {'SCG_BENCH_BACKEND': 'gloo', 'SCG_BENCH_PPO_GLOO': '1'})
+    out = _torchrun(['bench.py', '--gpus', '2', '--steps', '200', '--warmup', '50', '--full', '--ppo-seeds', '1', '--ppo-seconds', '3',
+                     '--ppo-envs', '16384'], {'SCG_BENCH_BACKEND': 'gloo', 'SCG_BENCH_PPO_GLOO': '1'})
     lines = [l for l in out.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out
     r = json.loads(lines[0])
@@ -109,8 +109,8 @@ def test_train_ppo_two_ranks_stay_in_lock_step(tmp_path):
 def test_bench_sac_leg_two_ranks_on_one_gpu():
     """bench.py's SAC leg with two ranks (BASELINE config #5 is SAC on 8 GPUs; the driver's N > 1 runs execute it over RCCL): env
     shards, replay shards, the data-parallel fused step, rank 0's clock."""
-    out = _torchrun(['bench.py', '--gpus', '2', '--steps', '200', '--warmup', '50', '--ppo-seeds', '0', '--sac-seeds', '1', '--sac-seconds', '6'],
-                    {'SCG_BENCH_BACKEND': 'gloo', 'SCG_BENCH_SAC_GLOO': '1'})
+    out = _torchrun(['bench.py', '--gpus', '2', '--steps', '200', '--warmup', '50', '--full', '--ppo-seeds', '0', '--sac-seeds', '1',
+                     '--sac-seconds', '6'], {'SCG_BENCH_BACKEND': 'gloo', 'SCG_BENCH_SAC_GLOO': '1'})
     lines = [l for l in out.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out
     r = json.loads(lines[0])
@@ -144,8 +144,9 @@ def test_bench_four_ranks_on_one_gpu_headline_and_ppo_leg():
     all-reduce, asynchronous evaluation per rank and rank 0's stop-flag broadcast, one JSON line from rank 0.  (No scaling number is
     meaningful here — four processes time-slice one device; `rccl_ranks: 0` says so in the line.  Four ranks, not eight: with this
     test's own process, at most five processes hold one shared GPU at a time.)"""
-    out = _torchrun(['bench.py', '--gpus', '4', '--steps', '200', '--warmup', '50', '--envs', '16384', '--ppo-seeds', '1', '--ppo-seconds', '4',
-                     '--ppo-envs', '4096', '--sac-seeds', '0'], {'SCG_BENCH_BACKEND': 'gloo', 'SCG_BENCH_PPO_GLOO': '1'}, timeout=900, nproc=4)
+    out = _torchrun(['bench.py', '--gpus', '4', '--steps', '200', '--warmup', '50', '--envs', '16384', '--full', '--ppo-seeds', '1',
+                     '--ppo-seconds', '4', '--ppo-envs', '4096', '--sac-seeds', '0'],
+                    {'SCG_BENCH_BACKEND': 'gloo', 'SCG_BENCH_PPO_GLOO': '1'}, timeout=900, nproc=4)
     lines = [l for l in out.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out
     r = json.loads(lines[0])

@@ -6,8 +6,9 @@
       csrc — pass a scratch copy to leave the product untouched) with the extra flags, stamped with the tree's source hash so that
       `SCG_SPEC_TAG=<tag>` loads it, and runs the store-hazard lint on it;
   run (GPU box):          python tools/ab_variant.py run <tag> [--tasks ...] [--rounds 2] [--envs 65536,262144] [--no-gate]
-      alternates `bench.py --task T` (headline only) with SCG_SPEC_TAG=<tag> and without, prints the launch periods, then the float32
-      one-step errors of the variant against the oracle (512 envs x 60 re-synchronised steps) — the quick gate before the full suite;
+      alternates `bench.py --task T --full --no-secondary` (headline + roofline) with SCG_SPEC_TAG=<tag> and without, prints the
+      launch periods, then the float32 one-step errors of the variant against the oracle (512 envs x 60 re-synchronised steps) —
+      the quick gate before the full suite;
   clean:                  python tools/ab_variant.py clean <tag>
 """
 import argparse
@@ -50,7 +51,7 @@ def build(tag, src, flags, tasks, sched=None):
 
 
 def run(tag, tasks, rounds, envs=(65536,), gate=True):
-    base = ['--steps', '4000', '--warmup', '500', '--no-secondary', '--no-cpu-baseline', '--ppo-seeds', '0', '--sac-seeds', '0']
+    base = ['--steps', '4000', '--warmup', '500', '--full', '--no-secondary', '--no-cpu-baseline', '--ppo-seeds', '0', '--sac-seeds', '0']
     for task, n_envs in ((t, e) for t in tasks for e in envs):
         for _ in range(rounds):
             for t in (tag, ''):

@@ -11,7 +11,7 @@ variants = {
 }
 for name, ov in variants.items():
     env = dict(os.environ, SCG_BENCH_OVERRIDE=json.dumps(ov))
-    out = subprocess.run([sys.executable, 'bench.py', '--steps', '5000', '--warmup', '500', '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, 'bench.py', '--steps', '5000', '--warmup', '500', '--full', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=200, env=env)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])

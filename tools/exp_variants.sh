@@ -17,7 +17,7 @@ run)
   for f in $SPEC/exp/*.so; do
     cp "$f" $SPEC/libscg_spec_$H.so
     printf "%-60s " "$(basename $f .so)"
-    timeout 120 python bench.py --no-cpu-baseline $2 < /dev/null 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('%.3f us/launch' % d['roofline']['avg_launch_us'])"
+    timeout 120 python bench.py --full --no-cpu-baseline $2 < /dev/null 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().split('\n')[-1]); print('%.3f us/launch' % d['roofline']['avg_launch_us'])"
   done
   cp /tmp/keep.so $SPEC/libscg_spec_$H.so ;;
 esac
