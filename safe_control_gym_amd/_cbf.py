@@ -1,0 +1,104 @@
+"""ctypes binding + builder of libscg_cbfroll_<spechash>_<hidden>_<activation>.so (include/scg_cbf.h): the CBF-QP safety filter as a
+batched certify kernel and as the policy rollout with the filter between the actor and the env step, compiled per task config and
+actor shape from csrc/scg_cbf.hip.  The filter's own settings travel by value (CbfParams): one library serves every filter config.
+The library carries every scg_hip.h entry point as well (_lib.EXPORTS): HipVecEnv(..., policy=(hidden, activation), cbf=True) drives
+its handle with it.  No fallback lives here: a shape or a system the library does not serve is an error."""
+import ctypes as C
+import os
+import subprocess
+
+from safe_control_gym_amd import _adversarial
+from safe_control_gym_amd import _lib as L
+
+SRC = os.path.join(L.CSRC_DIR, 'scg_cbf.hip')
+HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_cbf.h'))
+# the env library's hash inputs (_lib.SOURCES + _lib.HEADERS), the adversarial header the ABI includes, and the two new files
+DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, SRC, HEADER]
+PREFIX = 'libscg_cbfroll_'
+
+
+class CbfParams(C.Structure):
+    """scg_cbf_params (include/scg_cbf.h)."""
+    _fields_ = [('L', C.c_float * 4)] + [(n, C.c_float) for n in ('m', 'M', 'l', 'g', 'slope', 'slack_weight', 'slack_tolerance', 'lo', 'hi')] + \
+               [('soft', C.c_int32)]
+
+
+def supported(env_id, obs_dim, hidden, act_dim, activation):
+    """The filter serves the cartpole (the reference's CBF raises for every other system) with the fused policy rollout's actor shapes."""
+    return env_id == 'cartpole' and act_dim == 1 and obs_dim in (4, 8) and L.policy_supported(obs_dim, hidden, act_dim, activation)
+
+
+def source_hash():
+    import hashlib
+    h = hashlib.sha256()
+    for p in DEPS:
+        with open(p, 'rb') as f:
+            h.update(os.path.basename(p).encode() + b'\0' + f.read())
+    return int.from_bytes(h.digest()[:8], 'little')
+
+
+def lib_path(spec_hash, hidden, activation):
+    return os.path.join(L.SPEC_DIR, f'{PREFIX}{spec_hash:016x}_{int(hidden)}_{activation}.so')
+
+
+def build(cfg, hidden, activation, force=False):
+    """Compile the filter library for this scg_config and actor shape (hipcc, gfx950)."""
+    if activation not in L.POLICY_ACTS:
+        raise L.ScgError(f'no fused CBF rollout for activation {activation}')
+    src, h = L.spec_source(cfg)
+    hdr, _ = L.spec_paths(h)
+    so = lib_path(h, hidden, activation)
+    if not force and os.path.exists(so) and L._lib_source_hash(so) == source_hash():
+        return so
+    os.makedirs(L.SPEC_DIR, exist_ok=True)
+    with open(hdr, 'w') as f:
+        f.write(src)
+    cmd = [L._hipcc(), '--offload-arch=gfx950', '-O3', '-ffp-contract=on', '-std=c++17', '-fPIC', '-shared', '-DSCG_SPEC', '-include', hdr,
+           f'-DSCG_POLICY_H={int(hidden)}', f'-DSCG_POLICY_ACT={L.POLICY_ACTS[activation]}', f'-DSCG_SRC_HASH=0x{source_hash():016x}ULL', '-o', so]
+    res = None
+    for extra in L.sched_flags(cfg):
+        res = subprocess.run(cmd + extra + [SRC], capture_output=True, text=True)
+        if res.returncode == 0:
+            return so
+    raise L.ScgError('hipcc failed (CBF rollout build):\n' + res.stdout + res.stderr)
+
+
+_libs = {}
+
+
+def lib_for(cfg, hidden, activation):
+    """The bound library (every _lib.EXPORTS symbol + scg_cbf_certify / scg_rollout_cbf), built now if missing or stale."""
+    _, h = L.spec_source(cfg)
+    key = (h, int(hidden), activation)
+    if key in _libs:
+        return _libs[key]
+    so = lib_path(*key)
+    if not os.path.exists(so) or L._lib_source_hash(so) != source_hash():
+        if not os.path.exists(L._hipcc()):
+            raise L.ScgError(f'{so} is missing or stale and hipcc is not available to build it')
+        build(cfg, hidden, activation, force=True)
+    D = L._bind(so)
+    if int(D.scg_spec_hash()) != h:
+        raise L.ScgError(f'{so} was built for another config')
+    D.scg_cbf_certify.argtypes = [C.c_void_p, C.POINTER(CbfParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_void_p]
+    D.scg_rollout_cbf.argtypes = [C.c_void_p, C.POINTER(_adversarial.ActorPtrs), C.POINTER(CbfParams), C.c_int, C.c_int,
+                                  C.POINTER(L.PolicyRollout), C.c_void_p, C.c_void_p, C.c_void_p]
+    D.scg_cbf_shape.argtypes = [C.POINTER(C.c_int32)] * 4
+    if shape_of(D)[:2] != (int(hidden), L.POLICY_ACTS[activation]):
+        raise L.ScgError(f'{so} was built for another actor shape or another system')
+    _libs[key] = D
+    return D
+
+
+def shape_of(D):
+    """(hidden, activation id, obs_dim, act_dim) of a bound library (zeros: its task is not the cartpole)."""
+    v = [C.c_int32() for _ in range(4)]
+    D.scg_cbf_shape(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def actor_ptrs_of_policy(policy):
+    """ActorPtrs of an _lib.Policy (flat float32 parameter vector + word offsets)."""
+    base = int(policy.d_params)
+    return _adversarial.ActorPtrs(*[base + 4 * int(getattr(policy, n)) for n in ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'logstd_off')])

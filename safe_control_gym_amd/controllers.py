@@ -117,6 +117,8 @@ class HipController:
         self.env.close()
         if getattr(self, 'eval_env', None) is not None:
             self.eval_env.close()
+        if getattr(self, '_run_env_cbf', None) is not None:
+            self._run_env_cbf.close()
 
     def save(self, path):
         self.impl.save(path)
@@ -141,13 +143,30 @@ class HipController:
                 nz.read_only = frozen
             return self._act_module().act(o).cpu().numpy()
 
-    def run(self, env=None, render=False, n_episodes=10, verbose=False, **kwargs):
+    def run(self, env=None, render=False, n_episodes=10, verbose=False, safety_filter=None, **kwargs):
         """ppo.py:210-257: evaluation with the current (deterministic) policy — here `n_episodes` episodes side by side, one
-        per env of the evaluation env.  Returns the reference's dict: ep_returns, ep_lengths (+ constraint_violation, mse)."""
+        per env of the evaluation env.  Returns the reference's dict: ep_returns, ep_lengths (+ constraint_violation, mse).
+        safety_filter: a cbf.CBF — every action passes through the filter (base_experiment.py:177-184) in ONE fused launch; the result
+        gains `safety_filter_data` (per-env steps / corrected_steps / infeasible_steps / mean_correction)."""
         from safe_control_gym_amd.ppo import evaluate
         if render:
             raise NotImplementedError('no renderer: the simulator has no GUI')
         ev = env if isinstance(env, HipVecEnv) else None
+        if safety_filter is not None:
+            if ev is None:
+                if getattr(self, '_run_env_cbf', None) is None or self._run_env_cbf.num_envs != n_episodes:
+                    self._run_env_cbf = HipVecEnv(self.env_id, n_episodes, seed=self.seed * 111, return_numpy=False, policy=self._policy_shape(),
+                                                  cbf=True, **self.task_config)
+                ev = self._run_env_cbf
+            if getattr(self, 'norm_obs', False) or not getattr(self.impl, '_fused_rollout', False):
+                raise L.ScgError('run(safety_filter=) needs the fused rollout path without observation normalisation')
+            res = evaluate(self._act_module(), ev, policy=self.impl._policy_struct(True), safety_filter=safety_filter)
+            a = ev._eval_cbf['acc']
+            out = {'ep_returns': a[:, 1].double().cpu().numpy(), 'ep_lengths': a[:, 2].double().cpu().numpy(),
+                   'constraint_violation': a[:, 3].double().cpu().numpy(), 'mse': a[:, 4].double().cpu().numpy(),
+                   'safety_filter_data': {k: v.double().cpu().numpy() for k, v in res['safety_filter_data'].items()}}
+            self.results_dict = out
+            return out
         if ev is None:
             if getattr(self, '_run_env', None) is None or self._run_env.num_envs != n_episodes:
                 self._run_env = self._vec(n_episodes, self.seed * 111, self._policy_shape())

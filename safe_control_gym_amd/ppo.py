@@ -1018,6 +1018,42 @@ def _evaluate_fused_device(env, policy, episodes_per_env=1, chunk=None):
     return torch.stack([a[:, 0].sum(), a[:, 1].sum() / n, a[:, 2].sum() / n, a[:, 3].sum() / n, a[:, 4].sum() / n]), a
 
 
+@torch.no_grad()
+def _evaluate_cbf_device(env, policy, safety_filter, episodes_per_env=1):
+    """_evaluate_fused_device with the CBF filter between the actor and the env step (scg_rollout_cbf, deterministic): the same totals,
+    plus per-env filter statistics over the steps of each env's first `episodes_per_env` episodes — `steps`, `corrected_steps`
+    (|u* - u0| > 1e-6 on a feasible row, the reference example's threshold), `infeasible_steps` (the policy's own action was applied)
+    and `mean_correction` (mean |u* - u0| of the feasible rows), float32 [N] device tensors."""
+    from safe_control_gym_amd import _cbf
+    N, dev = env.num_envs, env.device
+    steps = env.spec.max_episode_steps * episodes_per_env
+    buf = getattr(env, '_eval_cbf', None)
+    if buf is None or buf['rew'].shape[0] != steps:
+        f = dict(device=dev, dtype=torch.float32)
+        nobs, nu = env.spec.obs_dim, env.spec.nu
+        buf = {'obs': torch.zeros(steps + 1, N, nobs, **f), 'act': torch.zeros(steps, N, nu, **f),
+               'logp': torch.zeros(steps, N, **f), 'rew': torch.zeros(steps, N, **f),
+               'done': torch.zeros(steps, N, dtype=torch.uint8, device=dev), 'flags': torch.zeros(steps, N, dtype=torch.uint8, device=dev),
+               'acc': torch.zeros(N, 8, **f), 'rows': torch.zeros(steps, N, 4, **f), 'applied': torch.zeros(steps, N, **f)}
+        env._eval_cbf = buf
+    env.reset_tensors()
+    buf['acc'].zero_()
+    env.rollout_cbf(_cbf.actor_ptrs_of_policy(policy), safety_filter.params(), steps, buf['obs'], buf['act'], buf['logp'], buf['rew'],
+                    buf['done'], buf['flags'], buf['rows'], buf['applied'], deterministic=True, episode_acc=buf['acc'],
+                    max_episodes=episodes_per_env)
+    a = buf['acc']
+    n = a[:, 0].sum().clamp(min=1.0)
+    res = torch.stack([a[:, 0].sum(), a[:, 1].sum() / n, a[:, 2].sum() / n, a[:, 3].sum() / n, a[:, 4].sum() / n])
+    done = buf['done'].to(torch.float32)
+    valid = ((done.cumsum(0) - done) < episodes_per_env).to(torch.float32)              # steps of the first episodes_per_env episodes
+    rows = buf['rows']
+    feas = rows[..., 3] * valid
+    corr = (rows[..., 1] - rows[..., 0]).abs()
+    data = {'steps': valid.sum(0), 'corrected_steps': ((corr > 1e-6).to(torch.float32) * feas).sum(0),
+            'infeasible_steps': ((1.0 - rows[..., 3]) * valid).sum(0), 'mean_correction': (corr * feas).sum(0) / feas.sum(0).clamp(min=1.0)}
+    return res, a, data
+
+
 def _evaluate_fused_result(res, a, episodes_per_env=1):
     out = {'episodes': res[0], 'ep_return': res[1], 'ep_length': res[2], 'ep_constraint_violation': res[3], 'ep_mse': res[4]}
     if episodes_per_env == 1 and a is not None:
@@ -1081,16 +1117,28 @@ class AsyncEvaluator:
 
 
 @torch.no_grad()
-def evaluate(ac, env, episodes_per_env=1, use_graph=None, obs_normalizer=None, policy=None):
+def evaluate(ac, env, episodes_per_env=1, use_graph=None, obs_normalizer=None, policy=None, safety_filter=None):
     """Deterministic policy (action = mean, ppo_utils.py:233-238) on every env of `env` until each finished
     `episodes_per_env` episodes; returns mean episode return / length / violations / mse (batched counterpart of
     PPO.run, ppo.py:210-257).  An episode lasts at most CTRL_STEPS control steps, so the loop has a fixed length and no
     host synchronisation; on a GPU it is captured once per (policy, env) pair and replayed as one HIP graph.
     policy: an _lib.Policy with deterministic = 1 (PPO._policy_struct(True)) for an env built with that policy shape —
-    the whole evaluation is then ONE launch of the fused rollout kernel."""
+    the whole evaluation is then ONE launch of the fused rollout kernel.
+    safety_filter: a cbf.CBF — every action passes through the filter before the env step (experiments/base_experiment.py:177-184), as
+    ONE launch of scg_rollout_cbf on an env built with policy= and cbf=True; the result gains `safety_filter_data`.  There is no
+    unfused filtered evaluation: without such an env (or without `policy`, or with an observation normaliser) this raises."""
     N = env.num_envs
     steps = env.spec.max_episode_steps * episodes_per_env
     dev = env.device
+    if safety_filter is not None:
+        if policy is None or obs_normalizer is not None or getattr(env, 'cbf_shape', None) is None:
+            from safe_control_gym_amd import _lib as L
+            raise L.ScgError('evaluate(safety_filter=) needs an env built with policy=(hidden, activation), cbf=True, the policy struct of '
+                             'that shape and no observation normaliser: the filtered evaluation exists only as the fused launch')
+        res, a, data = _evaluate_cbf_device(env, policy, safety_filter, episodes_per_env)
+        out = _evaluate_fused_result(res.tolist(), a, episodes_per_env)
+        out['safety_filter_data'] = data
+        return out
     if policy is not None and obs_normalizer is None and getattr(env, 'policy_shape', None) is not None:
         res, a = _evaluate_fused_device(env, policy, episodes_per_env)
         return _evaluate_fused_result(res.tolist(), a, episodes_per_env)

@@ -110,3 +110,7 @@ register(idx='quadrotor', entry_point='safe_control_gym_amd.benchmark_env:Quadro
 for _idx, _cls in (('ppo', 'PPO'), ('sac', 'SAC'), ('ddpg', 'DDPG'), ('rarl', 'RARL'), ('rap', 'RAP'), ('safe_explorer_ppo', 'SafeExplorerPPO')):
     register(idx=_idx, entry_point=f'safe_control_gym_amd.controllers:{_cls}',
              config_entry_point=f'safe_control_gym_amd.controllers:{_idx.upper()}_DEFAULTS')
+
+# safety-filter ids of the reference (safety_filters/__init__.py registers 'cbf', 'cbf_nn', 'linear_mpsc'): the analytic CBF-QP filter;
+# 'cbf_nn' (a 256 x 256 residual network) and 'linear_mpsc' (an MPC solve per step) are out of scope
+register(idx='cbf', entry_point='safe_control_gym_amd.cbf:CBF', config_entry_point='safe_control_gym_amd.cbf:CBF_DEFAULTS')

@@ -32,7 +32,8 @@ class _Dense:
 
 class _Names:
     """Display-only stand-in for a CasADi symbol vector: `str()` reads like CasADi's (`vertcat(x, x_dot, ...)`), `.shape` is (n, 1).
-    Not an expression graph — controllers that BUILD on the symbols (MPC, CBF, MPSC: out of scope) need CasADi."""
+    Not an expression graph — controllers that BUILD on the symbols (MPC, MPSC: out of scope) need CasADi; the CBF
+    filter does not: its Lie derivative is restated in closed form (cbf.py, csrc/scg_cbf.hip)."""
 
     def __init__(self, names):
         self.names = tuple(names)

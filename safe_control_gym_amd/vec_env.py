@@ -200,7 +200,7 @@ class HipVecEnv(VecEnv):
     """N independent copies of one environment stepped by libscg_hip.so on one GPU."""
 
     def __init__(self, env_id, num_envs, seed=0, device=None, dtype=torch.float32, env_id_offset=0,
-                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, safety_layer=None, **task_config):
+                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, safety_layer=None, cbf=False, **task_config):
         L.lib()                                        # fail loudly, before touching torch.cuda
         if not torch.cuda.is_available():
             raise L.ScgError('HipVecEnv needs a HIP device (torch.cuda.is_available() is False); '
@@ -255,8 +255,22 @@ class HipVecEnv(VecEnv):
                                                                          spec.n_state_con_rows, safety_layer):
                 hc = safety_layer[0] if isinstance(safety_layer, (list, tuple)) else safety_layer
                 self.safety_shape = self.policy_shape + (int(hc),)
+        # cbf=True (with policy=): the library that also carries the CBF safety filter (certify_tensors / rollout_cbf below) for the
+        # actor's shape; the filter serves the cartpole only, and there is no fallback: a system or shape it cannot serve is an error
+        self.cbf_shape = None
+        if cbf:
+            from safe_control_gym_amd import _cbf
+            if adversaries is not None or safety_layer is not None:
+                raise ValueError('cbf=True cannot be combined with adversaries= or safety_layer=')
+            if env_id != 'cartpole':
+                raise NotImplementedError('[Error] Currently CBF is only implemented for the cartpole system.')
+            if self.policy_shape is None or not _cbf.supported(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1]):
+                raise L.ScgError('cbf=True needs a float32 env and policy=(hidden, activation) of a shape the fused policy rollout serves')
+            self.cbf_shape = self.policy_shape
         if self.adversary_shape is not None:
             self._lib, self.specialized = _adversarial.lib_for(cfg, *self.adversary_shape), True
+        elif self.cbf_shape is not None:
+            self._lib, self.specialized = _cbf.lib_for(cfg, *self.cbf_shape), True
         elif self.safety_shape is not None:
             from safe_control_gym_amd import _safe_explorer
             self._lib, self.specialized = _safe_explorer.lib_for(cfg, *self.safety_shape), True
@@ -463,6 +477,54 @@ class HipVecEnv(VecEnv):
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_safe(self._h, C.byref(actor), p(safety), p(slack), int(bool(deterministic)), int(k_steps),
                                                  C.byref(o), p(c_rows), p(c_carry), self._stream()))
+
+    def certify_tensors(self, params, states, actions, certified=None, slack=None, feasible=None):
+        """The CBF-QP's minimiser for n (state, physical action) rows in ONE launch (scg_cbf_certify): `params` an _cbf.CbfParams
+        (cbf.CBF.params()), `states` float32 [n, 4], `actions` float32 [n]; n is independent of the env count.  Returns (and fills, when
+        passed) certified [n], slack [n] float32 and feasible [n] uint8."""
+        if self.cbf_shape is None:
+            raise L.ScgError('this env was not built with the CBF filter (HipVecEnv(..., policy=(hidden, activation), cbf=True))')
+        if states.dim() != 2 or states.shape[1] != 4 or actions.shape != (states.shape[0],):
+            raise ValueError('states must be [n, 4] and actions [n]')
+        n = int(states.shape[0])
+        if certified is None:
+            certified = torch.empty(n, dtype=torch.float32, device=self.device)
+        if slack is None:
+            slack = torch.empty(n, dtype=torch.float32, device=self.device)
+        if feasible is None:
+            feasible = torch.empty(n, dtype=torch.uint8, device=self.device)
+        for t, dt in ((states, torch.float32), (actions, torch.float32), (certified, torch.float32), (slack, torch.float32), (feasible, torch.uint8)):
+            if t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('states, actions, certified, slack (float32) and feasible (uint8) must be contiguous tensors on the env device')
+        if certified.numel() != n or slack.numel() != n or feasible.numel() != n:
+            raise ValueError(f'certified, slack and feasible must hold {n} entries')
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_cbf_certify(self._h, C.byref(params), p(states), p(actions), p(certified), p(slack), p(feasible), n,
+                                                self._stream()))
+        return certified, slack, feasible
+
+    def rollout_cbf(self, actor, params, k_steps, obs, act, logp, reward, done, flags, filter_rows, applied, deterministic=False,
+                    terminal_obs=None, episode_acc=None, max_episodes=0):
+        """K control steps in ONE launch with the actor AND the CBF filter in the loop (scg_rollout_cbf): `actor` is an
+        _adversarial.ActorPtrs, `params` an _cbf.CbfParams; filter_rows [K, N, 4] receives (u0, u*, s*, feasible) of every step,
+        applied [K, N] the (normalised) action given to the env step; act / logp keep the policy's own action and its log-probability;
+        the other arguments are as for rollout_policy."""
+        if self.cbf_shape is None:
+            raise L.ScgError('this env was not built with the CBF filter (HipVecEnv(..., policy=(hidden, activation), cbf=True))')
+        if filter_rows.shape != (int(k_steps), self.num_envs, 4) or applied.shape != (int(k_steps), self.num_envs):
+            raise ValueError(f'filter_rows must be [{int(k_steps)}, {self.num_envs}, 4] and applied [{int(k_steps)}, {self.num_envs}]')
+        for t in (filter_rows, applied):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('filter_rows and applied must be contiguous float32 tensors on the env device')
+        o = L.PolicyRollout()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        o.d_obs, o.d_act, o.d_logp, o.d_reward, o.d_done, o.d_flags = p(obs), p(act), p(logp), p(reward), p(done), p(flags)
+        o.d_terminal_obs, o.d_ep_stats, o.d_episode_acc = p(terminal_obs), p(self.ep_stats), p(episode_acc)
+        o.max_episodes = int(max_episodes)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_cbf(self._h, C.byref(actor), C.byref(params), int(bool(deterministic)), int(k_steps), C.byref(o),
+                                                p(filter_rows), p(applied), self._stream()))
 
     def step_sequence(self, actions, adv_actions=None, out=None, terminal_obs=True, mse=False, c_values=False, fin_stats=False,
                       state=False, noisy_action=False):
