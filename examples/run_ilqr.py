@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""iLQR from a grid of CartPole initial states, one independent problem per env, next to the LQR baseline from the same states: the
+stabilisation task of the reference's examples/lqr (ctrl_freq 15, pyb_freq 750, quadratic cost; tests/golden/ilqr_settings.json), the
+cart position and the pole angle swept.  Each LQR evaluation and each iLQR iteration is one closed-loop launch (scg_rollout_feedback);
+the iLQR backward pass is one more (scg_ilqr_backward).  Prints the LQR cost and the iLQR cost per state.
+
+usage: run_ilqr.py [--points 8] [--iterations 15] [--dtype float64]"""
+import argparse
+import json
+import os
+import sys
+from functools import partial
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from safe_control_gym_amd.registration import make  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--points', type=int, default=8, help='grid points per swept dimension')
+    ap.add_argument('--iterations', type=int, default=15)
+    ap.add_argument('--dtype', default='float64', choices=['float32', 'float64'])
+    a = ap.parse_args()
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ilqr_settings.json')) as f:
+        case = json.load(f)['cases']['cartpole_stab']
+    env_func = partial(make, case['env'], **case['task'])
+    xs, ths = np.linspace(-1.5, 0.5, a.points), np.linspace(-0.3, 0.3, a.points)
+    x0 = np.array([[x, 0.0, th, 0.0] for x in xs for th in ths])
+    algo = dict(case['algo'], max_iterations=a.iterations)
+    lqr = make('lqr', env_func, num_envs=len(x0), dtype=a.dtype, init_states=x0, q_lqr=algo['q_lqr'], r_lqr=algo['r_lqr'])
+    lqr_cost = -lqr.run()['ep_returns']
+    lqr.close()
+    ilqr = make('ilqr', env_func, num_envs=len(x0), dtype=a.dtype, init_states=x0, **algo)
+    ilqr.learn()
+    ilqr_cost = -ilqr.run()['ep_returns']
+    unstable, best_it, lamb = (np.atleast_1d(v) for v in (ilqr.initial_policy_unstable, ilqr.best_iteration, ilqr.lamb))
+    print(f'{"x":>7} {"theta":>7} {"LQR cost":>12} {"iLQR cost":>12} {"best it":>8} {"lambda":>8}')
+    for i, s in enumerate(x0):
+        note = '  (LQR leaves the bounds: no iLQR update)' if unstable[i] else ''
+        print(f'{s[0]:7.3f} {s[2]:7.3f} {lqr_cost[i]:12.5f} {ilqr_cost[i]:12.5f} {int(best_it[i]):8d} {lamb[i]:8.1f}{note}')
+    ilqr.close()
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,366 @@
+"""The reference's baseline controllers LQR and iLQR (controllers/lqr/{lqr,ilqr}.py) on the HIP engine, for a batch of envs.
+
+    ctrl = make('ilqr', env_func, num_envs=4096, init_states=x0, **ILQR_DEFAULTS)       # registration.py
+    ctrl.learn()                    # one independent iLQR problem per env
+    ctrl.run()                      # closed loop with every env's best schedule
+
+One env is one problem: its own initial state (and, with randomized_inertial_prop, its own inertial parameters), its own lambda, its
+own accept / reject history.  Per iLQR iteration the device runs ONE `scg_rollout_feedback` launch (the closed loop of every env with
+its current schedule), a handful of elementwise [N] tensor ops (the accept / reject / converged bookkeeping of ilqr.py:117-181), and ONE
+`scg_ilqr_backward` launch masked to the envs that update (include/scg_ilqr.h).  The LQR gain is one small matrix shared by all envs:
+A, B of the prior model at (X_EQ, U_EQ), Euler-discretised, the discrete Riccati equation solved on the host in NumPy.
+
+The one difference from upstream a caller can see: every env's initial state is FIXED for the whole of `learn` (init_states[i], or what
+the env's first reset drew); every iteration restarts from it.  Upstream calls a bare `env.reset()` per iteration and so, with
+randomized_init on, compares costs of different initial states (its shipped configs switch randomized_init off).
+
+Served: `lqr` on all four systems; `ilqr` on CartPole, Quadrotor 1D and 2D (Quadrotor 3D raises NotImplementedError: include/scg_ilqr.h).
+The env takes physical actions (normalized_rl_action_space off) and observes its state (cost: quadratic).  No CPU path.
+"""
+import ctypes as C
+
+import numpy as np
+
+from safe_control_gym_amd import _lib as L
+from safe_control_gym_amd.env_config import EnvSpec
+from safe_control_gym_amd.record_episode_statistics import resolve_env_func
+from safe_control_gym_amd.symbolic import AnalyticModel
+
+# controllers/lqr/lqr.yaml, ilqr.yaml
+LQR_DEFAULTS = dict(q_lqr=[1], r_lqr=[0.1], discrete_dynamics=True)
+ILQR_DEFAULTS = dict(q_lqr=[1], r_lqr=[0.1], discrete_dynamics=True, max_iterations=15, lamb_factor=10, lamb_max=1000, epsilon=0.01)
+
+FLAG_OOB = 4                    # include/scg_hip.h: SCG_FLAG_OUT_OF_BOUNDS
+
+
+def get_cost_weight_matrix(weights, dim):
+    """lqr_utils.py:77-99."""
+    weights = list(np.asarray(weights, dtype=float).reshape(-1))
+    if len(weights) == dim:
+        return np.diag(weights)
+    if len(weights) == 1:
+        return np.diag(weights * dim)
+    raise Exception('Wrong dimension for cost weights.')
+
+
+def discretize_linear_system(A, B, dt):
+    """lqr_utils.py:42-74 with exact=False."""
+    return np.eye(A.shape[0]) + A * dt, B * dt
+
+
+def solve_dare(A, B, Q, R, iterations=64, tol=1e-15):
+    """The stabilising solution of P = A'PA - A'PB (R + B'PB)^-1 B'PA + Q by the structure-preserving doubling algorithm (quadratic
+    convergence: G -> B R^-1 B' accumulated, H -> P), then polished by Riccati iterations.  NumPy only."""
+    n = A.shape[0]
+    Ak, G, H = A.copy(), B @ np.linalg.solve(R, B.T), Q.copy()
+    for _ in range(iterations):
+        W = np.linalg.inv(np.eye(n) + G @ H)
+        A1 = Ak @ W @ Ak
+        G1 = G + Ak @ W @ G @ Ak.T
+        H1 = H + Ak.T @ H @ W @ Ak
+        done = np.linalg.norm(H1 - H) <= tol * np.linalg.norm(H1)
+        Ak, G, H = A1, G1, H1
+        if done:
+            break
+    P = 0.5 * (H + H.T)
+    for _ in range(4):
+        btp = B.T @ P
+        P = A.T @ P @ A - (A.T @ P @ B) @ np.linalg.solve(R + btp @ B, btp @ A) + Q
+        P = 0.5 * (P + P.T)
+    return P
+
+
+def compute_lqr_gain(model, x_0, u_0, Q, R, discrete_dynamics=True):
+    """lqr_utils.py:7-39 on the analytic prior model; the Riccati equation is solved by solve_dare."""
+    df = model.df_func(x_0, u_0)
+    A, B = df[0].toarray(), df[1].toarray()
+    if not discrete_dynamics:
+        raise NotImplementedError('the continuous-time Riccati equation is not served: discrete_dynamics must be True')
+    A, B = discretize_linear_system(A, B, model.dt)
+    P = solve_dare(A, B, Q, R)
+    btp = B.T @ P
+    return np.linalg.solve(R + btp @ B, btp @ A)
+
+
+class LQR:
+    """Linear quadratic regulator (controllers/lqr/lqr.py) closing the loop of `num_envs` envs in one launch."""
+
+    def __init__(self, env_func, q_lqr=None, r_lqr=None, discrete_dynamics=True, num_envs=1, dtype='float64', init_states=None,
+                 prior_info=None, training=True, checkpoint_path='temp/model_latest.pt', output_dir='temp', use_gpu=True, seed=0, **kwargs):
+        self.env_func, self.training, self.checkpoint_path, self.output_dir, self.use_gpu, self.seed = \
+            env_func, training, checkpoint_path, output_dir, use_gpu, seed
+        self.prior_info = prior_info
+        for k, v in kwargs.items():
+            setattr(self, k, v)
+        self.q_lqr = LQR_DEFAULTS['q_lqr'] if q_lqr is None else q_lqr
+        self.r_lqr = LQR_DEFAULTS['r_lqr'] if r_lqr is None else r_lqr
+        self.discrete_dynamics = discrete_dynamics
+        self.num_envs = int(num_envs)
+        self.dtype_name = str(dtype).replace('torch.', '')
+        if self.dtype_name not in ('float32', 'float64'):
+            raise ValueError('dtype must be float32 or float64')
+        self.env_id, self.task_config = resolve_env_func(env_func)
+        for k in ('output_dir', 'seed', 'num_envs', 'return_numpy', 'device'):
+            self.task_config.pop(k, None)
+        self._configure_task()
+        self.spec = EnvSpec(self.env_id, dict(self.task_config))
+        spec = self.spec
+        if spec.kw.get('normalized_rl_action_space', False):
+            raise ValueError('lqr / ilqr compute physical actions: the env must have normalized_rl_action_space=False')
+        if spec.obs_dim != spec.nx:
+            raise ValueError('lqr / ilqr need an env that observes its state (cost: quadratic)')
+        self._check_system()
+        self.model = self.get_prior()
+        self.Q = get_cost_weight_matrix(self.q_lqr, self.model.nx)
+        self.R = get_cost_weight_matrix(self.r_lqr, self.model.nu)
+        self.gain = compute_lqr_gain(self.model, self.model.X_EQ, self.model.U_EQ, self.Q, self.R, self.discrete_dynamics)
+        self.stepsize = self.model.dt
+        self.max_steps = int(round(spec.CTRL_FREQ * spec.EPISODE_LEN_SEC))
+        self.init_states = None if init_states is None else np.asarray(init_states, dtype=np.float64).reshape(self.num_envs, -1)
+        self._venv = None
+        self._x0 = None
+        self.results_dict = {}
+
+    def _configure_task(self):
+        pass
+
+    def _check_system(self):
+        pass
+
+    # ---- the prior model (base_controller.py:134-193 on the analytic stand-in)
+    def get_prior(self, prior_info=None):
+        info = prior_info or self.prior_info or {}
+        return AnalyticModel(self.env_id, self.spec, dict(info.get('prior_prop') or {}))
+
+    def prior_params(self):
+        """The prior model's inertial parameters in scg_get_params' order."""
+        p = self.model.params
+        if self.env_id == 'cartpole':
+            return [p['length'], p['M'], p['m']]
+        return [p['m'], p['Ixx'], p['Iyy'], p['Izz']]
+
+    # ---- the shared LQR schedule: K_t = -gain, ff_t = gain X_GOAL[t] + U_EQ   (ilqr.py:314-337, lqr.py:68-90)
+    def lqr_schedule(self):
+        goal = np.atleast_2d(np.asarray(self.spec.X_GOAL, dtype=np.float64))
+        if self.spec.TASK == 'traj_tracking':
+            goal = goal[:self.max_steps]
+        K = np.repeat(-self.gain[None], goal.shape[0], axis=0)
+        ff = goal @ self.gain.T + self.model.U_EQ[None]
+        return K, ff
+
+    # ---- the device side
+    def _env(self):
+        if self._venv is None:
+            import torch
+            from safe_control_gym_amd.vec_env import HipVecEnv
+            self._torch = torch
+            self._tdtype = torch.float64 if self.dtype_name == 'float64' else torch.float32
+            self._venv = HipVecEnv(self.env_id, self.num_envs, seed=self.seed, dtype=self._tdtype, return_numpy=False, auto_reset=False,
+                                   ilqr=True, **self.task_config)
+            self._venv.reset_tensors()
+            if self.init_states is not None:
+                if self.init_states.shape[1] != self._venv._n_state_arrays():
+                    raise NotImplementedError('init_states are raw simulator states: this system\'s raw state is not its state vector')
+                self._venv.set_raw_state(self.init_states)
+            self._x0 = self._venv.get_raw_state()
+            self._snap = self._venv.ilqr_snapshot()                 # the fixed initial states, on the device
+        return self._venv
+
+    def set_params(self, params, first=0):
+        """Per-env inertial parameters of the TRUE envs (HipVecEnv.set_params; needs randomized_inertial_prop); they are kept by learn / run."""
+        self._env().set_params(params, first)
+
+    def set_initial_states(self, states):
+        """Raw simulator states [N, ns] every learn iteration and every run restarts from."""
+        venv = self._env()
+        venv.set_raw_state(np.asarray(states, dtype=np.float64).reshape(self.num_envs, -1))
+        self._x0 = venv.get_raw_state()
+        self._snap = venv.ilqr_snapshot()
+
+    def _restart(self):
+        """Every env back at its fixed initial state, step counter 0: a device-to-device copy, no host work."""
+        self._env().ilqr_restart(self._snap)
+
+    def _buffers(self):
+        if getattr(self, '_buf', None) is None:
+            torch, venv = self._torch, self._env()
+            N, T, nx, nu = self.num_envs, self.max_steps, self.spec.nx, self.spec.nu
+            f = dict(dtype=self._tdtype, device=venv.device)
+            self._buf = dict(x=torch.zeros(T + 1, nx, N, **f), u=torch.zeros(T, nu, N, **f), final_obs=torch.zeros(nx, N, **f),
+                             stats=torch.zeros(4, N, **f), n_steps=torch.zeros(N, dtype=torch.int32, device=venv.device),
+                             final_flags=torch.zeros(N, dtype=torch.uint8, device=venv.device))
+        return self._buf
+
+    def _rollout(self, K, ff, per_env):
+        b = self._buffers()
+        self._env().rollout_feedback(K, ff, self.max_steps, b['x'][:self.max_steps], b['u'], b['final_obs'], b['stats'], b['n_steps'],
+                                     b['final_flags'], per_env=per_env)
+        return b
+
+    def _as_schedule(self, K, ff):
+        t = self._torch
+        venv = self._env()
+        return (t.as_tensor(np.ascontiguousarray(K), dtype=self._tdtype, device=venv.device).contiguous(),
+                t.as_tensor(np.ascontiguousarray(ff), dtype=self._tdtype, device=venv.device).contiguous())
+
+    def reset(self):
+        self._env()
+
+    def close(self):
+        if self._venv is not None:
+            self._venv.close()
+            self._venv = None
+
+    def learn(self, env=None, **kwargs):
+        """lqr.py: nothing to learn."""
+
+    def select_action(self, obs, info=None):
+        """lqr.py:68-90: -gain (x - x_goal) + U_EQ at the step info['current_step'] (batched obs [N, nx] are accepted)."""
+        step = 0 if info is None else int(info.get('current_step', 0))
+        goal = np.atleast_2d(np.asarray(self.spec.X_GOAL, dtype=np.float64))
+        g = goal[min(step, goal.shape[0] - 1)] if self.spec.TASK == 'traj_tracking' else goal[0]
+        return -(np.asarray(obs, dtype=np.float64) - g) @ self.gain.T + self.model.U_EQ
+
+    def _schedule_for_run(self):
+        K, ff = self.lqr_schedule()
+        return self._as_schedule(K, ff) + (False,)
+
+    def run(self, env=None, max_steps=None, **kwargs):
+        """The closed loop of every env from its initial state in ONE launch; the dict HipController.run returns."""
+        self._env()
+        self._restart()
+        K, ff, per_env = self._schedule_for_run()
+        b = self._rollout(K, ff, per_env)
+        stats = b['stats'].cpu().numpy().astype(np.float64)
+        n = np.maximum(stats[1], 1.0)
+        self.results_dict = {'obs': b['x'], 'action': b['u'], 'final_obs': b['final_obs'], 'n_steps': b['n_steps']}
+        return {'ep_returns': -stats[0], 'ep_lengths': stats[1].astype(np.int64), 'constraint_violation': stats[2], 'mse': stats[3] / n}
+
+
+class iLQR(LQR):
+    """Iterative linear quadratic regulator (controllers/lqr/ilqr.py), one independent problem per env."""
+
+    def __init__(self, env_func, q_lqr=None, r_lqr=None, discrete_dynamics=True, max_iterations=15, lamb_factor=10, lamb_max=1000,
+                 epsilon=0.01, **kwargs):
+        self.max_iterations, self.lamb_factor, self.lamb_max, self.epsilon = int(max_iterations), float(lamb_factor), float(lamb_max), float(epsilon)
+        super().__init__(env_func, q_lqr=q_lqr, r_lqr=r_lqr, discrete_dynamics=discrete_dynamics, **kwargs)
+        self.ite_counter = 0
+        self.input_ff_best = None
+        self.gains_fb_best = None
+        self.best_iteration = None
+        self.lamb = None
+        self.history = []
+
+    def _configure_task(self):
+        self.task_config['done_on_out_of_bound'] = True                 # ilqr.py:61
+
+    def _check_system(self):
+        if self.spec.nx == 12:
+            raise NotImplementedError('ilqr does not serve Quadrotor 3D: the backward kernel holds Sm and Ad in registers (12 x 12 each '
+                                      'do not fit) and inverts the Hessian in closed form (nu <= 2); lqr serves it')
+
+    def model_struct(self):
+        from safe_control_gym_amd import _ilqr
+        m = _ilqr.IlqrModel()
+        for k, v in enumerate(np.diag(self.Q)):
+            m.q[k] = float(v)
+        for k, v in enumerate(np.diag(self.R)):
+            m.r[k] = float(v)
+        for k, v in enumerate(self.model.U_EQ):
+            m.u_eq[k] = float(v)
+        for k, v in enumerate(self.prior_params()):
+            m.par[k] = float(v)
+        m.arm = float(self.model.params['L']) / np.sqrt(2.0) if self.env_id == 'quadrotor' else 0.0
+        m.dt = float(self.model.dt)
+        m.eps = 1e-6 if self.dtype_name == 'float64' else 1e-3           # HipVecEnv.prior_model's steps
+        return m
+
+    def learn(self, env=None, to_host=True, **kwargs):
+        """to_host=False keeps the results as device tensors only (no [N, T, nu, nx] copy to the host).
+        ilqr.py:84-183 for every env at once; no host synchronisation inside an iteration except the one all-finished check."""
+        venv = self._env()
+        torch = self._torch
+        N, T, nx, nu = self.num_envs, self.max_steps, self.spec.nx, self.spec.nu
+        f = dict(dtype=self._tdtype, device=venv.device)
+        K0, ff0 = self._as_schedule(*self.lqr_schedule())
+        s = torch.arange(T, device=venv.device).clamp(max=K0.shape[0] - 1)
+        # the per-env schedule [T][nu][nx][N] / [T][nu][N], initialised with the LQR one (iteration 0 itself runs the shared schedule)
+        gains = K0[s].unsqueeze(-1).expand(T, nu, nx, N).contiguous()
+        ff = ff0[s].unsqueeze(-1).expand(T, nu, N).contiguous()
+        gains_best, ff_best = gains.clone(), ff.clone()
+        lamb = torch.ones(N, **f)
+        prev_cost = torch.full((N,), -float('inf'), **f)
+        best_it = torch.zeros(N, dtype=torch.int32, device=venv.device)
+        improved = torch.zeros(N, dtype=torch.bool, device=venv.device)
+        finished = torch.zeros(N, dtype=torch.bool, device=venv.device)
+        unstable = torch.zeros(N, dtype=torch.uint8, device=venv.device)
+        have_best = torch.zeros(N, dtype=torch.bool, device=venv.device)
+        ite = torch.zeros(N, dtype=torch.int32, device=venv.device)
+        model = self.model_struct()
+        self.history = []
+        b = self._buffers()
+        for it in range(self.max_iterations):
+            self._restart()
+            if it == 0:
+                self._rollout(K0, ff0, False)
+            else:
+                self._rollout(gains, ff, True)
+            cost = b['stats'][0]
+            n_steps = b['n_steps']
+            # final observation -> row n_steps of the x stack (ilqr.py:112)
+            b['x'].scatter_(0, n_steps.long().view(1, 1, N).expand(1, nx, N), b['final_obs'].unsqueeze(0))
+            active = ~finished
+            if it == 0:
+                oob = (b['final_flags'] & FLAG_OOB) != 0
+                finished = finished | oob                                # ilqr.py:117-119
+                update = active & ~oob
+                accept, reject, conv = update, torch.zeros_like(update), torch.zeros_like(update)
+            else:
+                delta = cost - prev_cost
+                reject = active & ((delta > 0) | (unstable != 0))
+                accept = active & ~reject
+                conv = accept & (delta.abs() < self.epsilon) & improved
+                update = accept & ~conv
+                lamb = torch.where(reject, torch.clamp(lamb * self.lamb_factor, max=self.lamb_max), lamb)
+                unstable.masked_fill_(reject, 0)
+                torch.where(reject.view(1, 1, 1, N), gains_best, gains, out=gains)
+                torch.where(reject.view(1, 1, N), ff_best, ff, out=ff)
+                finished = finished | conv
+            improved = torch.where(active, accept & (it > 0), improved)
+            best_it = torch.where(accept, torch.full_like(best_it, it), best_it)
+            prev_cost = torch.where(accept, cost, prev_cost)
+            torch.where(accept.view(1, 1, 1, N), gains, gains_best, out=gains_best)
+            torch.where(accept.view(1, 1, N), ff, ff_best, out=ff_best)
+            have_best = have_best | accept
+            self.history.append(dict(cost=cost.clone(), lamb=lamb.clone(), accept=accept, reject=reject, converged=conv,
+                                     active=active, n_steps=n_steps.clone()))
+            venv.ilqr_backward(model, T, b['x'], b['u'], n_steps, lamb, update.to(torch.uint8), gains, ff, unstable)
+            ite = torch.where(active & ~finished, ite + 1, ite)
+            if bool(finished.all()):                                     # the one host check of the iteration
+                break
+        self._gains, self._ff = gains, ff
+        self._gains_best_t, self._ff_best_t, self._have_best = gains_best, ff_best, have_best
+        self._best_cost_t, self._lamb_t, self._best_it_t = prev_cost, lamb, best_it
+        if not to_host:
+            return
+        squeeze = (lambda a: a[0]) if N == 1 else (lambda a: a)
+        # the reference's shapes, with a leading env axis when num_envs > 1: gains_fb [T, nu, nx], input_ff [nu, T]
+        self.gains_fb_best = squeeze(gains_best.permute(3, 0, 1, 2).cpu().numpy().astype(np.float64))
+        self.input_ff_best = squeeze(ff_best.permute(2, 1, 0).cpu().numpy().astype(np.float64))
+        self.best_iteration = squeeze(best_it.cpu().numpy())
+        self.lamb = squeeze(lamb.cpu().numpy().astype(np.float64))
+        self.best_cost = squeeze(prev_cost.cpu().numpy().astype(np.float64))
+        self.ite_counter = squeeze(ite.cpu().numpy())
+        self.initial_policy_unstable = squeeze((~have_best).cpu().numpy())
+
+    def select_action(self, obs, info=None, training=False):
+        """ilqr.py:280-312 outside training: the best schedule at step info['current_step'] (one env), else the LQR law."""
+        if self.gains_fb_best is None or self.num_envs != 1:
+            return LQR.select_action(self, obs, info)
+        step = min(0 if info is None else int(info.get('current_step', 0)), self.max_steps - 1)
+        return self.gains_fb_best[step] @ np.asarray(obs, dtype=np.float64) + self.input_ff_best[:, step]
+
+    def _schedule_for_run(self):
+        if getattr(self, '_gains_best_t', None) is None:
+            return LQR._schedule_for_run(self)
+        return self._gains_best_t, self._ff_best_t, True

@@ -200,7 +200,7 @@ class HipVecEnv(VecEnv):
     """N independent copies of one environment stepped by libscg_hip.so on one GPU."""
 
     def __init__(self, env_id, num_envs, seed=0, device=None, dtype=torch.float32, env_id_offset=0,
-                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, safety_layer=None, cbf=False, **task_config):
+                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, safety_layer=None, cbf=False, ilqr=False, **task_config):
         L.lib()                                        # fail loudly, before touching torch.cuda
         if not torch.cuda.is_available():
             raise L.ScgError('HipVecEnv needs a HIP device (torch.cuda.is_available() is False); '
@@ -267,7 +267,14 @@ class HipVecEnv(VecEnv):
             if self.policy_shape is None or not _cbf.supported(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1]):
                 raise L.ScgError('cbf=True needs a float32 env and policy=(hidden, activation) of a shape the fused policy rollout serves')
             self.cbf_shape = self.policy_shape
-        if self.adversary_shape is not None:
+        # ilqr=True: the library that also carries the LQR / iLQR controllers' kernels (rollout_feedback / ilqr_backward below)
+        self.ilqr = bool(ilqr)
+        if self.ilqr and (policy is not None or adversaries is not None or safety_layer is not None or cbf):
+            raise ValueError('ilqr=True cannot be combined with policy=, adversaries=, safety_layer= or cbf=')
+        if self.ilqr:
+            from safe_control_gym_amd import _ilqr
+            self._lib, self.specialized = _ilqr.lib_for(cfg), True
+        elif self.adversary_shape is not None:
             self._lib, self.specialized = _adversarial.lib_for(cfg, *self.adversary_shape), True
         elif self.cbf_shape is not None:
             self._lib, self.specialized = _cbf.lib_for(cfg, *self.cbf_shape), True
@@ -525,6 +532,72 @@ class HipVecEnv(VecEnv):
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_cbf(self._h, C.byref(actor), C.byref(params), int(bool(deterministic)), int(k_steps), C.byref(o),
                                                 p(filter_rows), p(applied), self._stream()))
+
+    def rollout_feedback(self, gains, ff, k_steps, x, u, final_obs, stats, n_steps, final_flags, per_env=False, reward=None, done=None,
+                         flags=None):
+        """K control steps in ONE launch with the affine feedback u = gains[t] obs + ff[t] in the loop (scg_rollout_feedback,
+        include/scg_ilqr.h): gains [T, nu, nx] / ff [T, nu] shared by every env, or per_env [T, nu, nx, N] / [T, nu, N]; the schedule index
+        saturates at T - 1.  Fills x [K, nx, N], u [K, nu, N], final_obs [nx, N], stats [4, N] (cost, steps, violations, mse sum),
+        n_steps int32 [N], final_flags uint8 [N] and, when passed, reward / done / flags [K, N].  An env stops at its first done; rows
+        past it are not written."""
+        if not self.ilqr:
+            raise L.ScgError('this env was not built with the LQR / iLQR kernels (HipVecEnv(..., ilqr=True))')
+        from safe_control_gym_amd import _ilqr
+        N, nx, nu, K = self.num_envs, self.spec.nx, self.spec.nu, int(k_steps)
+        T = int(gains.shape[0])
+        want = {'gains': (T, nu, nx, N) if per_env else (T, nu, nx), 'ff': (T, nu, N) if per_env else (T, nu), 'x': (K, nx, N), 'u': (K, nu, N),
+                'final_obs': (nx, N), 'stats': (4, N)}
+        have = {'gains': gains, 'ff': ff, 'x': x, 'u': u, 'final_obs': final_obs, 'stats': stats}
+        for k, t in have.items():
+            if tuple(t.shape) != want[k] or t.dtype != self.dtype or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f'{k} must be a contiguous {list(want[k])} {self.dtype} tensor on the env device')
+        for k, t, dt, shape in (('n_steps', n_steps, torch.int32, (N,)), ('final_flags', final_flags, torch.uint8, (N,)),
+                                ('done', done, torch.uint8, (K, N)), ('flags', flags, torch.uint8, (K, N)), ('reward', reward, self.dtype, (K, N))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f'{k} must be a contiguous {list(shape)} {dt} tensor on the env device')
+        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        io = _ilqr.FeedbackRollout(p(gains), p(ff), T, int(bool(per_env)), p(x), p(u), p(final_obs), p(stats), p(n_steps), p(final_flags),
+                                   p(reward), p(done), p(flags))
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_feedback(self._h, K, C.byref(io), self._stream()))
+
+    def ilqr_backward(self, model, k_steps, x, u, n_steps, lamb, mask, gains, ff, unstable):
+        """iLQR's backward pass for every env whose mask byte is set, ONE launch (scg_ilqr_backward, include/scg_ilqr.h): `model` an
+        _ilqr.IlqrModel, x [K + 1, nx, N] (row n_steps[i] = env i's final observation), u [K, nu, N], n_steps int32 [N], lamb [N],
+        mask uint8 [N] or None; gains [K, nu, nx, N] and ff [K, nu, N] are updated in place, unstable uint8 [N] is set where the
+        Hessian was not finite."""
+        if not self.ilqr:
+            raise L.ScgError('this env was not built with the LQR / iLQR kernels (HipVecEnv(..., ilqr=True))')
+        N, nx, nu, K = self.num_envs, self.spec.nx, self.spec.nu, int(k_steps)
+        for k, t, dt, shape in (('x', x, self.dtype, (K + 1, nx, N)), ('u', u, self.dtype, (K, nu, N)), ('n_steps', n_steps, torch.int32, (N,)),
+                                ('lamb', lamb, self.dtype, (N,)), ('mask', mask, torch.uint8, (N,)), ('gains', gains, self.dtype, (K, nu, nx, N)),
+                                ('ff', ff, self.dtype, (K, nu, N)), ('unstable', unstable, torch.uint8, (N,))):
+            if t is None and k == 'mask':
+                continue
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f'{k} must be a contiguous {list(shape)} {dt} tensor on the env device')
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_ilqr_backward(self._h, C.byref(model), K, p(x), p(u), p(n_steps), p(lamb), p(mask), p(gains), p(ff),
+                                                  p(unstable), self._stream()))
+
+    def ilqr_snapshot(self):
+        """Every env's raw simulator state as a device tensor [ns, N] (scg_ilqr_snapshot); ilqr_restart(snapshot) puts it back and zeroes
+        the step counters, without host work."""
+        if not self.ilqr:
+            raise L.ScgError('this env was not built with the LQR / iLQR kernels (HipVecEnv(..., ilqr=True))')
+        snap = torch.empty(self._n_state_arrays(), self.num_envs, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_ilqr_snapshot(self._h, C.c_void_p(snap.data_ptr()), self._stream()))
+        return snap
+
+    def ilqr_restart(self, snap):
+        if not self.ilqr:
+            raise L.ScgError('this env was not built with the LQR / iLQR kernels (HipVecEnv(..., ilqr=True))')
+        if tuple(snap.shape) != (self._n_state_arrays(), self.num_envs) or snap.dtype != self.dtype or not snap.is_contiguous() or snap.device != self.device:
+            raise ValueError('snap must be the tensor ilqr_snapshot returned')
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_ilqr_restart(self._h, C.c_void_p(snap.data_ptr()), self._stream()))
 
     def step_sequence(self, actions, adv_actions=None, out=None, terminal_obs=True, mse=False, c_values=False, fin_stats=False,
                       state=False, noisy_action=False):
