@@ -1,6 +1,6 @@
 """ctypes binding + builder of libscg_ilqr_<spechash>.so (include/scg_ilqr.h): the LQR / iLQR baseline controllers' two kernels — the
-closed-loop rollout with an affine time-varying state feedback in the loop and iLQR's backward pass — compiled per task config from
-csrc/scg_ilqr.hip.  The controllers' own settings (Q, R, the prior model's parameters) travel by value: one library serves every
+closed-loop rollout with an affine time-varying state feedback in the loop and iLQR's backward pass — and the PID baseline's rollout
+(include/scg_pid.h, csrc/scg_pid.h), compiled per task config from csrc/scg_ilqr.hip.  The controllers' own settings (Q, R, the prior model's parameters) travel by value: one library serves every
 controller config of its task.  The library carries every scg_hip.h entry point as well (_lib.EXPORTS): HipVecEnv(..., ilqr=True)
 drives its handle with it.  No fallback lives here: a system or an env config the library does not serve is an error."""
 import ctypes as C
@@ -11,7 +11,9 @@ from safe_control_gym_amd import _lib as L
 
 SRC = os.path.join(L.CSRC_DIR, 'scg_ilqr.hip')
 HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_ilqr.h'))
-DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [SRC, HEADER]
+PID_SRC = os.path.join(L.CSRC_DIR, 'scg_pid.h')                    # the PID rollout: included by scg_ilqr.hip
+PID_HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_pid.h'))
+DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [SRC, HEADER, PID_SRC, PID_HEADER]
 PREFIX = 'libscg_ilqr_'
 
 
@@ -19,6 +21,19 @@ class FeedbackRollout(C.Structure):
     """scg_feedback_rollout (include/scg_ilqr.h)."""
     _fields_ = [('d_gains', C.c_void_p), ('d_ff', C.c_void_p), ('schedule_len', C.c_int32), ('per_env', C.c_int32), ('d_x', C.c_void_p),
                 ('d_u', C.c_void_p), ('d_final_obs', C.c_void_p), ('d_stats', C.c_void_p), ('d_n_steps', C.c_void_p),
+                ('d_final_flags', C.c_void_p), ('d_reward', C.c_void_p), ('d_done', C.c_void_p), ('d_flags', C.c_void_p)]
+
+
+class PidConfig(C.Structure):
+    """scg_pid_config (include/scg_pid.h)."""
+    _fields_ = [('kf', C.c_double), ('gravity', C.c_double), ('pwm2rpm_scale', C.c_double), ('pwm2rpm_const', C.c_double), ('min_pwm', C.c_double),
+                ('max_pwm', C.c_double), ('dt', C.c_double)]
+
+
+class PidRollout(C.Structure):
+    """scg_pid_rollout (include/scg_pid.h)."""
+    _fields_ = [('d_gains', C.c_void_p), ('per_env', C.c_int32), ('reserved', C.c_int32), ('d_pid_state', C.c_void_p), ('config', PidConfig),
+                ('d_x', C.c_void_p), ('d_u', C.c_void_p), ('d_final_obs', C.c_void_p), ('d_stats', C.c_void_p), ('d_n_steps', C.c_void_p),
                 ('d_final_flags', C.c_void_p), ('d_reward', C.c_void_p), ('d_done', C.c_void_p), ('d_flags', C.c_void_p)]
 
 
@@ -66,7 +81,7 @@ _libs = {}
 
 
 def lib_for(cfg):
-    """The bound library (every _lib.EXPORTS symbol + scg_rollout_feedback / scg_ilqr_backward), built now if missing or stale."""
+    """The bound library (every _lib.EXPORTS symbol + scg_rollout_feedback / scg_ilqr_backward / scg_rollout_pid), built now if missing or stale."""
     _, h = L.spec_source(cfg)
     if h in _libs:
         return _libs[h]
@@ -82,5 +97,6 @@ def lib_for(cfg):
     D.scg_ilqr_backward.argtypes = [C.c_void_p, C.POINTER(IlqrModel), C.c_int] + [C.c_void_p] * 9
     D.scg_ilqr_snapshot.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     D.scg_ilqr_restart.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    D.scg_rollout_pid.argtypes = [C.c_void_p, C.c_int, C.POINTER(PidRollout), C.c_void_p]
     _libs[h] = D
     return D

@@ -7,7 +7,8 @@
 //                             differences of prior_model_kernel (same EnvOps::sym_f), the Hessian's eigen-decomposition in closed form.
 //
 // Built only as   hipcc ... -DSCG_SPEC -include <spec header> scg_ilqr.hip   (safe_control_gym_amd/_ilqr.py); the simulator's
-// translation unit is included whole, without any edit to it.
+// translation unit is included whole, without any edit to it.  The PID baseline's rollout (scg_pid.h, include/scg_pid.h) is included at
+// the end: one library per task config serves lqr, ilqr and pid.
 #include "scg_kernels.hip"
 
 #include "../../include/scg_ilqr.h"
@@ -429,3 +430,5 @@ extern "C" int scg_ilqr_restart(scg_env* env, const void* d_state, void* stream)
     HIP_TRY(hipMemsetAsync(env->d_step, 0, (size_t)env->cfg.num_envs * 4, (hipStream_t)stream));
     return SCG_OK;
 }
+
+#include "scg_pid.h"

@@ -82,19 +82,17 @@ def compute_lqr_gain(model, x_0, u_0, Q, R, discrete_dynamics=True):
     return np.linalg.solve(R + btp @ B, btp @ A)
 
 
-class LQR:
-    """Linear quadratic regulator (controllers/lqr/lqr.py) closing the loop of `num_envs` envs in one launch."""
+class BatchedController:
+    """What the batched baseline controllers (LQR, iLQR here; PID in pid.py) share: the reference's base arguments, the task behind
+    `env_func`, the prior model, and the lazy device side — one HipVecEnv(..., ilqr=True) with fixed initial states that every rollout
+    restarts from."""
 
-    def __init__(self, env_func, q_lqr=None, r_lqr=None, discrete_dynamics=True, num_envs=1, dtype='float64', init_states=None,
-                 prior_info=None, training=True, checkpoint_path='temp/model_latest.pt', output_dir='temp', use_gpu=True, seed=0, **kwargs):
+    def _init_common(self, env_func, num_envs, dtype, init_states, prior_info, training, checkpoint_path, output_dir, use_gpu, seed, kwargs):
         self.env_func, self.training, self.checkpoint_path, self.output_dir, self.use_gpu, self.seed = \
             env_func, training, checkpoint_path, output_dir, use_gpu, seed
         self.prior_info = prior_info
         for k, v in kwargs.items():
             setattr(self, k, v)
-        self.q_lqr = LQR_DEFAULTS['q_lqr'] if q_lqr is None else q_lqr
-        self.r_lqr = LQR_DEFAULTS['r_lqr'] if r_lqr is None else r_lqr
-        self.discrete_dynamics = discrete_dynamics
         self.num_envs = int(num_envs)
         self.dtype_name = str(dtype).replace('torch.', '')
         if self.dtype_name not in ('float32', 'float64'):
@@ -102,51 +100,22 @@ class LQR:
         self.env_id, self.task_config = resolve_env_func(env_func)
         for k in ('output_dir', 'seed', 'num_envs', 'return_numpy', 'device'):
             self.task_config.pop(k, None)
-        self._configure_task()
-        self.spec = EnvSpec(self.env_id, dict(self.task_config))
-        spec = self.spec
-        if spec.kw.get('normalized_rl_action_space', False):
-            raise ValueError('lqr / ilqr compute physical actions: the env must have normalized_rl_action_space=False')
-        if spec.obs_dim != spec.nx:
-            raise ValueError('lqr / ilqr need an env that observes its state (cost: quadratic)')
-        self._check_system()
-        self.model = self.get_prior()
-        self.Q = get_cost_weight_matrix(self.q_lqr, self.model.nx)
-        self.R = get_cost_weight_matrix(self.r_lqr, self.model.nu)
-        self.gain = compute_lqr_gain(self.model, self.model.X_EQ, self.model.U_EQ, self.Q, self.R, self.discrete_dynamics)
-        self.stepsize = self.model.dt
-        self.max_steps = int(round(spec.CTRL_FREQ * spec.EPISODE_LEN_SEC))
-        self.init_states = None if init_states is None else np.asarray(init_states, dtype=np.float64).reshape(self.num_envs, -1)
+        self._init_states_arg = init_states
         self._venv = None
         self._x0 = None
         self.results_dict = {}
 
-    def _configure_task(self):
-        pass
-
-    def _check_system(self):
-        pass
+    def _init_episode(self):
+        """After self.spec exists: the episode length and the caller's initial states."""
+        spec = self.spec
+        self.max_steps = int(round(spec.CTRL_FREQ * spec.EPISODE_LEN_SEC))
+        init_states = self._init_states_arg
+        self.init_states = None if init_states is None else np.asarray(init_states, dtype=np.float64).reshape(self.num_envs, -1)
 
     # ---- the prior model (base_controller.py:134-193 on the analytic stand-in)
     def get_prior(self, prior_info=None):
         info = prior_info or self.prior_info or {}
         return AnalyticModel(self.env_id, self.spec, dict(info.get('prior_prop') or {}))
-
-    def prior_params(self):
-        """The prior model's inertial parameters in scg_get_params' order."""
-        p = self.model.params
-        if self.env_id == 'cartpole':
-            return [p['length'], p['M'], p['m']]
-        return [p['m'], p['Ixx'], p['Iyy'], p['Izz']]
-
-    # ---- the shared LQR schedule: K_t = -gain, ff_t = gain X_GOAL[t] + U_EQ   (ilqr.py:314-337, lqr.py:68-90)
-    def lqr_schedule(self):
-        goal = np.atleast_2d(np.asarray(self.spec.X_GOAL, dtype=np.float64))
-        if self.spec.TASK == 'traj_tracking':
-            goal = goal[:self.max_steps]
-        K = np.repeat(-self.gain[None], goal.shape[0], axis=0)
-        ff = goal @ self.gain.T + self.model.U_EQ[None]
-        return K, ff
 
     # ---- the device side
     def _env(self):
@@ -191,6 +160,61 @@ class LQR:
                              final_flags=torch.zeros(N, dtype=torch.uint8, device=venv.device))
         return self._buf
 
+    def reset(self):
+        self._env()
+
+    def close(self):
+        if self._venv is not None:
+            self._venv.close()
+            self._venv = None
+
+
+class LQR(BatchedController):
+    """Linear quadratic regulator (controllers/lqr/lqr.py) closing the loop of `num_envs` envs in one launch."""
+
+    def __init__(self, env_func, q_lqr=None, r_lqr=None, discrete_dynamics=True, num_envs=1, dtype='float64', init_states=None,
+                 prior_info=None, training=True, checkpoint_path='temp/model_latest.pt', output_dir='temp', use_gpu=True, seed=0, **kwargs):
+        self._init_common(env_func, num_envs, dtype, init_states, prior_info, training, checkpoint_path, output_dir, use_gpu, seed, kwargs)
+        self.q_lqr = LQR_DEFAULTS['q_lqr'] if q_lqr is None else q_lqr
+        self.r_lqr = LQR_DEFAULTS['r_lqr'] if r_lqr is None else r_lqr
+        self.discrete_dynamics = discrete_dynamics
+        self._configure_task()
+        self.spec = EnvSpec(self.env_id, dict(self.task_config))
+        spec = self.spec
+        if spec.kw.get('normalized_rl_action_space', False):
+            raise ValueError('lqr / ilqr compute physical actions: the env must have normalized_rl_action_space=False')
+        if spec.obs_dim != spec.nx:
+            raise ValueError('lqr / ilqr need an env that observes its state (cost: quadratic)')
+        self._check_system()
+        self.model = self.get_prior()
+        self.Q = get_cost_weight_matrix(self.q_lqr, self.model.nx)
+        self.R = get_cost_weight_matrix(self.r_lqr, self.model.nu)
+        self.gain = compute_lqr_gain(self.model, self.model.X_EQ, self.model.U_EQ, self.Q, self.R, self.discrete_dynamics)
+        self.stepsize = self.model.dt
+        self._init_episode()
+
+    def _configure_task(self):
+        pass
+
+    def _check_system(self):
+        pass
+
+    def prior_params(self):
+        """The prior model's inertial parameters in scg_get_params' order."""
+        p = self.model.params
+        if self.env_id == 'cartpole':
+            return [p['length'], p['M'], p['m']]
+        return [p['m'], p['Ixx'], p['Iyy'], p['Izz']]
+
+    # ---- the shared LQR schedule: K_t = -gain, ff_t = gain X_GOAL[t] + U_EQ   (ilqr.py:314-337, lqr.py:68-90)
+    def lqr_schedule(self):
+        goal = np.atleast_2d(np.asarray(self.spec.X_GOAL, dtype=np.float64))
+        if self.spec.TASK == 'traj_tracking':
+            goal = goal[:self.max_steps]
+        K = np.repeat(-self.gain[None], goal.shape[0], axis=0)
+        ff = goal @ self.gain.T + self.model.U_EQ[None]
+        return K, ff
+
     def _rollout(self, K, ff, per_env):
         b = self._buffers()
         self._env().rollout_feedback(K, ff, self.max_steps, b['x'][:self.max_steps], b['u'], b['final_obs'], b['stats'], b['n_steps'],
@@ -202,14 +226,6 @@ class LQR:
         venv = self._env()
         return (t.as_tensor(np.ascontiguousarray(K), dtype=self._tdtype, device=venv.device).contiguous(),
                 t.as_tensor(np.ascontiguousarray(ff), dtype=self._tdtype, device=venv.device).contiguous())
-
-    def reset(self):
-        self._env()
-
-    def close(self):
-        if self._venv is not None:
-            self._venv.close()
-            self._venv = None
 
     def learn(self, env=None, **kwargs):
         """lqr.py: nothing to learn."""

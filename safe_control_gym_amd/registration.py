@@ -115,9 +115,10 @@ for _idx, _cls in (('ppo', 'PPO'), ('sac', 'SAC'), ('ddpg', 'DDPG'), ('rarl', 'R
 # 'cbf_nn' (a 256 x 256 residual network) and 'linear_mpsc' (an MPC solve per step) are out of scope
 register(idx='cbf', entry_point='safe_control_gym_amd.cbf:CBF', config_entry_point='safe_control_gym_amd.cbf:CBF_DEFAULTS')
 
-# baseline controller ids of the reference (controllers/__init__.py: 'lqr', 'ilqr'), batched: one closed-loop launch per rollout, one
-# backward-pass launch per iLQR iteration (lqr.py, csrc/scg_ilqr.hip).  'pid' (a quadrotor-only position controller with integrator
-# state) is not served; 'ilqr' raises NotImplementedError for Quadrotor 3D.  tools/run_reference_example.py binds the REFERENCE's own
-# registry module, so its 'lqr' / 'ilqr' ids do not meet these.
+# baseline controller ids of the reference (controllers/__init__.py: 'lqr', 'ilqr', 'pid'), batched: one closed-loop launch per rollout,
+# one backward-pass launch per iLQR iteration (lqr.py, csrc/scg_ilqr.hip); 'pid' (pid.py, csrc/scg_pid.h) is the quadrotor-only cascade
+# PID with its integrator state carried inside the launch.  'ilqr' raises NotImplementedError for Quadrotor 3D, 'pid' for anything but
+# Quadrotor 2D / 3D.  tools/run_reference_example.py binds the REFERENCE's own registry module, so its ids do not meet these.
 register(idx='lqr', entry_point='safe_control_gym_amd.lqr:LQR', config_entry_point='safe_control_gym_amd.lqr:LQR_DEFAULTS')
 register(idx='ilqr', entry_point='safe_control_gym_amd.lqr:iLQR', config_entry_point='safe_control_gym_amd.lqr:ILQR_DEFAULTS')
+register(idx='pid', entry_point='safe_control_gym_amd.pid:PID', config_entry_point='safe_control_gym_amd.pid:PID_DEFAULTS')

@@ -561,6 +561,31 @@ class HipVecEnv(VecEnv):
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_feedback(self._h, K, C.byref(io), self._stream()))
 
+    def rollout_pid(self, gains, config, k_steps, x, u, final_obs, stats, n_steps, final_flags, pid_state=None, per_env=False, reward=None,
+                    done=None, flags=None):
+        """K control steps in ONE launch with the reference's cascade PID law in the loop (scg_rollout_pid, include/scg_pid.h): gains
+        [18] shared by every env or per_env [18, N] (P / I / D force, P / I / D torque, three values each), `config` an _ilqr.PidConfig,
+        pid_state [9, N] (position integral, last rpy, attitude integral: read at entry, written at exit) or None (zeros, discarded).
+        Outputs as rollout_feedback's.  Quadrotor 2D and 3D."""
+        if not self.ilqr:
+            raise L.ScgError('this env was not built with the LQR / iLQR / PID kernels (HipVecEnv(..., ilqr=True))')
+        from safe_control_gym_amd import _ilqr
+        N, nx, nu, K = self.num_envs, self.spec.nx, self.spec.nu, int(k_steps)
+        for k, t, dt, shape in (('gains', gains, self.dtype, (18, N) if per_env else (18,)), ('pid_state', pid_state, self.dtype, (9, N)),
+                                ('x', x, self.dtype, (K, nx, N)), ('u', u, self.dtype, (K, nu, N)), ('final_obs', final_obs, self.dtype, (nx, N)),
+                                ('stats', stats, self.dtype, (4, N)), ('n_steps', n_steps, torch.int32, (N,)),
+                                ('final_flags', final_flags, torch.uint8, (N,)), ('done', done, torch.uint8, (K, N)),
+                                ('flags', flags, torch.uint8, (K, N)), ('reward', reward, self.dtype, (K, N))):
+            if t is None and k in ('pid_state', 'done', 'flags', 'reward'):
+                continue
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f'{k} must be a contiguous {list(shape)} {dt} tensor on the env device')
+        p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        io = _ilqr.PidRollout(p(gains), int(bool(per_env)), 0, p(pid_state), config, p(x), p(u), p(final_obs), p(stats), p(n_steps),
+                              p(final_flags), p(reward), p(done), p(flags))
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_pid(self._h, K, C.byref(io), self._stream()))
+
     def ilqr_backward(self, model, k_steps, x, u, n_steps, lamb, mask, gains, ff, unstable):
         """iLQR's backward pass for every env whose mask byte is set, ONE launch (scg_ilqr_backward, include/scg_ilqr.h): `model` an
         _ilqr.IlqrModel, x [K + 1, nx, N] (row n_steps[i] = env i's final observation), u [K, nu, N], n_steps int32 [N], lamb [N],
