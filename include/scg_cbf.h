@@ -19,6 +19,7 @@
 
 #include <stdint.h>
 
+#include "scg_actor_rollout.h"
 #include "scg_adversarial.h"
 
 #ifdef __cplusplus
@@ -56,6 +57,13 @@ int scg_cbf_certify(scg_env* env, const scg_cbf_params* params, const float* d_s
  *   d_applied      float32 [k][N]    the (normalised) action given to the env step */
 int scg_rollout_cbf(scg_env* env, const scg_actor_ptrs* actor, const scg_cbf_params* params, int deterministic, int k_steps,
                     const scg_policy_rollout* out, float* d_filter_rows, float* d_applied, void* stream);
+
+/* The same with the deterministic SAC / DDPG actor of scg_actor_rollout.h in front of the filter (scg_rollout_actor's kernel with the
+ * certify step between the head and the env step): scg_rollout_cbf's row layout and applied-action rule; out.act keeps the actor's
+ * action, out.logp is not written.  Served by libscg_cbfroll_<spechash>_<H>_<act>_<sac|ddpg>.so (float32 CartPole); every other
+ * library returns SCG_ERR_INVALID, as does an actor whose hidden / activation / kind differ from the compiled ones. */
+int scg_rollout_cbf_actor(scg_env* env, const scg_actor* actor, const scg_cbf_params* params, int k_steps, const scg_policy_rollout* out,
+                          float* d_filter_rows, float* d_applied, void* stream);
 
 /* Compiled shape: actor hidden width and activation, observation and action dims (all 0 when the library's task is not CartPole:
  * both entry points then return SCG_ERR_INVALID). */

@@ -13,7 +13,9 @@ from safe_control_gym_amd import _lib as L
 SRC = os.path.join(L.CSRC_DIR, 'scg_cbf.hip')
 HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_cbf.h'))
 # the env library's hash inputs (_lib.SOURCES + _lib.HEADERS), the adversarial header the ABI includes, and the two new files
-DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, SRC, HEADER]
+DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, SRC, HEADER,
+                                                                         os.path.join(L.CSRC_DIR, 'scg_cbf_actor.h')] + \
+    [os.path.normpath(os.path.join(L.CSRC_DIR, d)) for d in L.ACTOR_DEPS[1:]]
 PREFIX = 'libscg_cbfroll_'
 
 
@@ -28,6 +30,12 @@ def supported(env_id, obs_dim, hidden, act_dim, activation):
     return env_id == 'cartpole' and act_dim == 1 and obs_dim in (4, 8) and L.policy_supported(obs_dim, hidden, act_dim, activation)
 
 
+def supported_actor(env_id, obs_dim, hidden, act_dim, activation, kind):
+    """The filter behind a SAC / DDPG actor (scg_rollout_cbf_actor): the cartpole with the fused actor rollout's shapes."""
+    return kind in L.ACTOR_KINDS and env_id == 'cartpole' and act_dim == 1 and obs_dim in (4, 8) and \
+        L.policy_supported(obs_dim, hidden, act_dim, activation)
+
+
 def source_hash():
     import hashlib
     h = hashlib.sha256()
@@ -37,17 +45,20 @@ def source_hash():
     return int.from_bytes(h.digest()[:8], 'little')
 
 
-def lib_path(spec_hash, hidden, activation):
-    return os.path.join(L.SPEC_DIR, f'{PREFIX}{spec_hash:016x}_{int(hidden)}_{activation}.so')
+def lib_path(spec_hash, hidden, activation, kind=None):
+    return os.path.join(L.SPEC_DIR, f'{PREFIX}{spec_hash:016x}_{int(hidden)}_{activation}{"_" + kind if kind else ""}.so')
 
 
-def build(cfg, hidden, activation, force=False):
-    """Compile the filter library for this scg_config and actor shape (hipcc, gfx950)."""
+def build(cfg, hidden, activation, kind=None, force=False):
+    """Compile the filter library for this scg_config and actor shape (hipcc, gfx950); kind 'sac' | 'ddpg': the variant that also
+    carries scg_rollout_actor / scg_rollout_cbf_actor for that actor."""
     if activation not in L.POLICY_ACTS:
         raise L.ScgError(f'no fused CBF rollout for activation {activation}')
+    if kind is not None and kind not in L.ACTOR_KINDS:
+        raise L.ScgError(f'no fused CBF rollout for actor kind {kind}')
     src, h = L.spec_source(cfg)
     hdr, _ = L.spec_paths(h)
-    so = lib_path(h, hidden, activation)
+    so = lib_path(h, hidden, activation, kind)
     if not force and os.path.exists(so) and L._lib_source_hash(so) == source_hash():
         return so
     os.makedirs(L.SPEC_DIR, exist_ok=True)
@@ -55,6 +66,8 @@ def build(cfg, hidden, activation, force=False):
         f.write(src)
     cmd = [L._hipcc(), '--offload-arch=gfx950', '-O3', '-ffp-contract=on', '-std=c++17', '-fPIC', '-shared', '-DSCG_SPEC', '-include', hdr,
            f'-DSCG_POLICY_H={int(hidden)}', f'-DSCG_POLICY_ACT={L.POLICY_ACTS[activation]}', f'-DSCG_SRC_HASH=0x{source_hash():016x}ULL', '-o', so]
+    if kind is not None:
+        cmd.append(f'-DSCG_POLICY_KIND={L.ACTOR_KINDS[kind]}')
     res = None
     for extra in L.sched_flags(cfg):
         res = subprocess.run(cmd + extra + [SRC], capture_output=True, text=True)
@@ -66,29 +79,47 @@ def build(cfg, hidden, activation, force=False):
 _libs = {}
 
 
-def lib_for(cfg, hidden, activation):
-    """The bound library (every _lib.EXPORTS symbol + scg_cbf_certify / scg_rollout_cbf), built now if missing or stale."""
+def bind(so):
+    """_lib._bind + the argument types of this header's entry points."""
+    D = L._bind(so)
+    D.scg_cbf_certify.argtypes = [C.c_void_p, C.POINTER(CbfParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.c_void_p]
+    D.scg_rollout_cbf.argtypes = [C.c_void_p, C.POINTER(_adversarial.ActorPtrs), C.POINTER(CbfParams), C.c_int, C.c_int,
+                                  C.POINTER(L.PolicyRollout), C.c_void_p, C.c_void_p, C.c_void_p]
+    D.scg_rollout_cbf_actor.argtypes = [C.c_void_p, C.POINTER(L.Actor), C.POINTER(CbfParams), C.c_int, C.POINTER(L.PolicyRollout),
+                                        C.c_void_p, C.c_void_p, C.c_void_p]
+    D.scg_cbf_shape.argtypes = [C.POINTER(C.c_int32)] * 4
+    return D
+
+
+def lib_for(cfg, hidden, activation, kind=None):
+    """The bound library (every _lib.EXPORTS symbol + scg_cbf_certify / scg_rollout_cbf / scg_rollout_cbf_actor), built now if
+    missing or stale."""
     _, h = L.spec_source(cfg)
-    key = (h, int(hidden), activation)
+    key = (h, int(hidden), activation) + ((kind,) if kind else ())
     if key in _libs:
         return _libs[key]
     so = lib_path(*key)
     if not os.path.exists(so) or L._lib_source_hash(so) != source_hash():
         if not os.path.exists(L._hipcc()):
             raise L.ScgError(f'{so} is missing or stale and hipcc is not available to build it')
-        build(cfg, hidden, activation, force=True)
-    D = L._bind(so)
+        build(cfg, hidden, activation, kind, force=True)
+    D = bind(so)
     if int(D.scg_spec_hash()) != h:
         raise L.ScgError(f'{so} was built for another config')
-    D.scg_cbf_certify.argtypes = [C.c_void_p, C.POINTER(CbfParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                  C.c_void_p]
-    D.scg_rollout_cbf.argtypes = [C.c_void_p, C.POINTER(_adversarial.ActorPtrs), C.POINTER(CbfParams), C.c_int, C.c_int,
-                                  C.POINTER(L.PolicyRollout), C.c_void_p, C.c_void_p, C.c_void_p]
-    D.scg_cbf_shape.argtypes = [C.POINTER(C.c_int32)] * 4
     if shape_of(D)[:2] != (int(hidden), L.POLICY_ACTS[activation]):
         raise L.ScgError(f'{so} was built for another actor shape or another system')
+    if kind and actor_shape_of(D) != (int(hidden), L.POLICY_ACTS[activation], L.ACTOR_KINDS[kind]):
+        raise L.ScgError(f'{so} was built for another actor kind')
     _libs[key] = D
     return D
+
+
+def actor_shape_of(D):
+    """(hidden, activation id, kind id) of the actor rollout a bound library carries (zeros: none)."""
+    v = [C.c_int32() for _ in range(3)]
+    D.scg_actor_rollout_shape(*[C.byref(x) for x in v])
+    return tuple(x.value for x in v)
 
 
 def shape_of(D):

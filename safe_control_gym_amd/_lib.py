@@ -14,6 +14,9 @@ LIB_PATH = os.path.join(PKG_DIR, 'libscg_hip.so')
 SOURCES = ['scg_kernels.hip']
 HEADERS = ['scg_env_core.h', 'scg_env_kernels.h', 'scg_gae_kernels.h', 'scg_mlp.h', 'scg_once.h', 'scg_params.h', 'scg_rng.h', 'scg_spec.h',
            os.path.join('..', '..', 'include', 'scg_hip.h')]         # (scg_mlp.h: the policy-in-the-loop variants include it)
+# the SAC / DDPG actor rollout's translation unit (policy=(hidden, activation, kind) variants): scg_kernels.hip included whole + these
+ACTOR_SOURCE = 'scg_actor_rollout.hip'
+ACTOR_DEPS = [ACTOR_SOURCE, 'scg_actor_rollout.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')]
 SPEC_DIR = os.path.join(PKG_DIR, 'spec')
 
 SCG_ABI_VERSION = 1
@@ -99,6 +102,12 @@ class PolicyRollout(C.Structure):
                                     'd_ep_stats', 'd_episode_acc')] + [('max_episodes', c_i32)]
 
 
+class Actor(C.Structure):
+    """scg_actor (include/scg_actor_rollout.h): the deterministic SAC / DDPG actor of the fused rollout."""
+    _fields_ = [('d_params', c_vp)] + [(n, c_i32) for n in ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'hidden', 'activation', 'kind')] + \
+               [('act_low', C.c_float * MAX_ACTION), ('act_high', C.c_float * MAX_ACTION)]
+
+
 class Sequence(C.Structure):
     _fields_ = [(n, c_vp) for n in ('d_actions', 'd_adv_actions', 'd_obs', 'd_reward', 'd_done', 'd_flags', 'd_terminal_obs',
                                     'd_mse', 'd_c_values', 'd_ep_stats', 'd_fin_stats', 'd_state', 'd_noisy_action')]
@@ -112,6 +121,7 @@ EXPORTS = ['scg_dims', 'scg_workspace_bytes', 'scg_create', 'scg_destroy', 'scg_
            'scg_rollout_random', 'scg_set_state', 'scg_get_state', 'scg_set_params', 'scg_get_params',
            'scg_set_counters', 'scg_get_counters', 'scg_set_seed', 'scg_set_step_launch', 'scg_set_step_wsback', 'scg_rng_layout_version', 'scg_gae', 'scg_prior_model', 'scg_last_error', 'scg_abi_version',
            'scg_sizeof_config', 'scg_sizeof_step_out', 'scg_spec_source', 'scg_spec_hash', 'scg_source_hash']
+ACTOR_EXPORTS = ['scg_rollout_actor', 'scg_actor_rollout_shape']       # (the kind variants and the CBF libraries only)
 
 
 class ScgError(RuntimeError):
@@ -136,6 +146,20 @@ def source_hash():
     h.update(CODEGEN_FLAGS.encode())
     h.update(b'sched:q2=max-ilp,q3=max-ilp,q3dist=iterative-ilp')              # (sched_flags below: part of what a library was built with)
     return int.from_bytes(h.digest()[:8], 'little')
+
+
+def actor_source_hash():
+    """source_hash() of the actor-rollout variants: the env library's inputs and the files of ACTOR_DEPS."""
+    import hashlib
+    h = hashlib.sha256(source_hash().to_bytes(8, 'little'))
+    for name in ACTOR_DEPS:
+        with open(os.path.normpath(os.path.join(CSRC_DIR, name)), 'rb') as f:
+            h.update(os.path.basename(name).encode() + b'\0' + f.read())
+    return int.from_bytes(h.digest()[:8], 'little')
+
+
+def _policy_hash(policy):
+    return actor_source_hash() if policy and len(policy) == 3 else source_hash()
 
 
 def _hipcc():
@@ -203,6 +227,9 @@ def _bind(path):
     L.scg_rollout_random.argtypes = [c_vp, C.c_int, C.POINTER(RolloutOut), c_vp]
     L.scg_rollout_policy.argtypes = [c_vp, C.POINTER(Policy), C.c_int, C.POINTER(PolicyRollout), c_vp]
     L.scg_step_sequence.argtypes = [c_vp, C.c_int, C.POINTER(Sequence), c_vp]
+    if all(hasattr(L, name) for name in ACTOR_EXPORTS):
+        L.scg_rollout_actor.argtypes = [c_vp, C.POINTER(Actor), C.c_int, C.POINTER(PolicyRollout), c_vp]
+        L.scg_actor_rollout_shape.argtypes = [C.POINTER(c_i32)] * 3
     for fn in (L.scg_set_state, L.scg_get_state, L.scg_set_params, L.scg_get_params):
         fn.argtypes = [c_vp, C.POINTER(c_f64), C.c_int, C.c_int, c_vp]
     L.scg_set_counters.argtypes = [c_vp, C.POINTER(c_i32), C.POINTER(C.c_uint32), C.c_int, C.c_int, c_vp]
@@ -246,15 +273,37 @@ def spec_source(cfg):
 
 
 POLICY_ACTS = {'tanh': 0, 'relu': 1, 'leaky_relu': 2}
+ACTOR_KINDS = {'sac': 1, 'ddpg': 2}                     # SCG_ACTOR_SAC, SCG_ACTOR_DDPG (include/scg_actor_rollout.h)
+
+
+def policy_tuple(policy):
+    """A policy= argument checked and normalised: None, (hidden, activation) or (hidden, activation, 'sac' | 'ddpg').  Raises
+    ValueError for anything else, before any file is named or built."""
+    if policy is None:
+        return None
+    if not isinstance(policy, (tuple, list)) or len(policy) not in (2, 3):
+        raise ValueError(f"policy must be (hidden, activation) or (hidden, activation, 'sac' | 'ddpg'), not {policy!r}")
+    if isinstance(policy[0], bool) or int(policy[0]) != policy[0] or int(policy[0]) <= 0:
+        raise ValueError(f'policy hidden width must be a positive integer, not {policy[0]!r}')
+    if policy[1] not in POLICY_ACTS:
+        raise ValueError(f'policy activation must be one of {sorted(POLICY_ACTS)}, not {policy[1]!r}')
+    if len(policy) == 3 and policy[2] not in ACTOR_KINDS:
+        raise ValueError(f'policy kind must be one of {sorted(ACTOR_KINDS)}, not {policy[2]!r}')
+    return (int(policy[0]), policy[1]) + tuple(policy[2:])
 
 
 def spec_paths(hash_value, policy=None):
     """(header, library) of a specialisation.  policy=(hidden, activation): the variant that also carries the fused
-    policy-in-the-loop rollout kernel (scg_rollout_policy) for that actor shape.  Development variants: SCG_SPEC_TAG=<name>
+    policy-in-the-loop rollout kernel (scg_rollout_policy) for that actor shape; policy=(hidden, activation, 'sac' | 'ddpg'): the one
+    that carries scg_rollout_actor for that actor as well.  Development variants: SCG_SPEC_TAG=<name>
     selects / builds libscg_spec_<hash>_<name>.so (compiled with the extra flags in SCG_SPEC_FLAGS)."""
     tag = f'{hash_value:016x}'
     var = os.environ.get('SCG_SPEC_TAG', '')
+    if policy and len(policy) != 2:
+        policy_tuple(policy)
     pol = f'_pol{policy[0]}_{policy[1]}' if policy else ''
+    if policy and len(policy) == 3:
+        pol += f'_{policy[2]}'
     return (os.path.join(SPEC_DIR, f'scg_spec_{tag}.h'),
             os.path.join(SPEC_DIR, f'libscg_spec_{tag}{pol}{"_" + var if var else ""}.so'))
 
@@ -286,20 +335,26 @@ def sched_flags(cfg):
 
 def build_spec(cfg, force=False, verbose=False, policy=None):
     """Compile libscg_spec_<hash>.so: the same sources with this task config as compile-time constants
-    (policy=(hidden, activation): + the fused policy rollout kernel for that actor shape)."""
+    (policy=(hidden, activation): + the fused policy rollout kernel for that actor shape; a third element 'sac' | 'ddpg': + the
+    actor rollout of that kind, scg_rollout_actor)."""
+    if policy and len(policy) != 2:
+        policy = policy_tuple(policy)
     src, h = spec_source(cfg)
     hdr, so = spec_paths(h, policy)
     os.makedirs(SPEC_DIR, exist_ok=True)
-    srcs = [os.path.join(CSRC_DIR, s) for s in SOURCES]
-    if not force and os.path.exists(so) and _lib_source_hash(so) == source_hash():
+    kind = bool(policy) and len(policy) == 3
+    srcs = [os.path.join(CSRC_DIR, s) for s in ([ACTOR_SOURCE] if kind else SOURCES)]
+    if not force and os.path.exists(so) and _lib_source_hash(so) == _policy_hash(policy):
         return so
     with open(hdr, 'w') as f:
         f.write(src)
     hipcc = _hipcc()
     cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-ffp-contract=on', '-std=c++17', '-fPIC', '-shared', '-DSCG_SPEC', '-include', hdr,
-           f'-DSCG_SRC_HASH=0x{source_hash():016x}ULL', '-o', so] + os.environ.get('SCG_SPEC_FLAGS', '').split()
+           f'-DSCG_SRC_HASH=0x{_policy_hash(policy):016x}ULL', '-o', so] + os.environ.get('SCG_SPEC_FLAGS', '').split()
     if policy:
         cmd += [f'-DSCG_POLICY_H={int(policy[0])}', f'-DSCG_POLICY_ACT={POLICY_ACTS[policy[1]]}']
+        if len(policy) == 3:
+            cmd.append(f'-DSCG_POLICY_KIND={ACTOR_KINDS[policy[2]]}')
     alts = [[]] if os.environ.get('SCG_SPEC_FLAGS') else sched_flags(cfg)       # (explicit development flags: nothing added)
     res = None
     for extra in alts:
@@ -316,6 +371,8 @@ def lib_for(cfg, specialize='auto', policy=None):
     """Library to drive an env with this config: the matching specialised build when it exists in-tree
     (or, with specialize=True, after compiling it now), else the generic library.  policy=(hidden, activation) asks for
     the variant with the fused policy rollout; it is compiled on demand (it cannot come from the generic library)."""
+    if policy and len(policy) != 2:
+        policy = policy_tuple(policy)
     if specialize in (False, 'off', None) and not policy:
         return lib(), False
     _, h = spec_source(cfg)
@@ -323,7 +380,7 @@ def lib_for(cfg, specialize='auto', policy=None):
     if key in _spec_libs:
         return _spec_libs[key], True
     _, so = spec_paths(h, policy)
-    stale = os.path.exists(so) and _lib_source_hash(so) != source_hash()
+    stale = os.path.exists(so) and _lib_source_hash(so) != _policy_hash(policy)
     if not os.path.exists(so) or stale:
         if policy or specialize is True or specialize == 'build' or (stale and os.path.exists(_hipcc())):
             build_spec(cfg, force=True, policy=policy)     # (stale: the kernel sources changed since it was compiled)
@@ -332,6 +389,8 @@ def lib_for(cfg, specialize='auto', policy=None):
     L = _bind(so)
     if int(L.scg_spec_hash()) != h:
         raise ScgError(f'{so} was built for another config')
+    if policy and len(policy) == 3 and not all(hasattr(L, name) for name in ACTOR_EXPORTS):
+        raise ScgError(f'{so} does not export {ACTOR_EXPORTS}')
     _spec_libs[key] = L
     return L, True
 

@@ -270,17 +270,55 @@ class RAP(RARL):
         return rarl.RAP(self.env, pcfg, seed=self.seed, num_adversaries=self.num_adversaries)
 
 
-class SAC(HipController):
+class _OffPolicy(HipController):
+    """What SAC and DDPG share.  Extension key `fused_rollout=True` (not in SAC_DEFAULTS / DDPG_DEFAULTS, which equal the YAML files):
+    the envs are built with the actor's shape and kind (HipVecEnv(..., policy=(hidden_dim, activation, 'sac' | 'ddpg'))), so that run()
+    and the evaluations inside learn() are ONE scg_rollout_actor launch, and run(safety_filter=) one scg_rollout_cbf_actor launch.  A
+    shape the kernel does not serve (hidden_dim 256, the YAML default), an agent off its fused path or a running normaliser warns once
+    and keeps the eager evaluation loop.  Training collection is unchanged either way."""
+    KIND = None
+
+    def _policy_shape(self):
+        if not self.algo_config.get('fused_rollout'):
+            return None
+        if not hasattr(self, '_fused_shape'):
+            from safe_control_gym_amd import _ddpg, _sac
+            from safe_control_gym_amd.env_config import EnvSpec
+            spec = EnvSpec(self.env_id, dict(self.task_config))
+            act = self.algo_config.get('activation', 'relu')
+            extra = self.algo_config
+            agent_fused = (_sac if self.KIND == 'sac' else _ddpg).supported(spec.obs_dim, self.hidden_dim, spec.nu, act) \
+                and bool(extra.get('cuda_graphs', True)) and bool(extra.get('fused_update', True))
+            ok = L.policy_supported(spec.obs_dim, self.hidden_dim, spec.nu, act) and spec.obs_dim in (spec.nx, 2 * spec.nx) \
+                and agent_fused and not (self.norm_obs or self.norm_reward)
+            if not ok:
+                import warnings
+                warnings.warn(f'{self.KIND}: fused_rollout=True is not served for hidden_dim {self.hidden_dim} / {act} / obs {spec.obs_dim} '
+                              f'(widths 32, 64, 96, 128 on the fused agent, no running normaliser): keeping the eager evaluation loop')
+            self._fused_shape = (int(self.hidden_dim), act, self.KIND) if ok else None
+        return self._fused_shape
+
+    def _mark_fused(self):
+        self.impl._fused_rollout = bool(self._policy_shape() is not None and self.impl.agent.use_fused)
+        if self._policy_shape() is not None and not self.impl._fused_rollout:       # (e.g. several ranks: the agent left its fused path)
+            import warnings
+            warnings.warn(f'{self.KIND}: fused_rollout=True, but the agent is not on its fused path (no flat parameter vector): keeping the '
+                          f'eager evaluation loop')
+
+
+class SAC(_OffPolicy):
     """controllers/sac/sac.py:35-335."""
     DEFAULTS = SAC_DEFAULTS
+    KIND = 'sac'
 
     def _build(self):
         from safe_control_gym_amd import sac
         scfg = sac.SACConfig.from_dict(self.algo_config)
         n = self.rollout_batch_size if self.training else self.eval_batch_size
-        self.env = self._vec(n, self.seed)
+        self.env = self._vec(n, self.seed, self._policy_shape())
         self.eval_env = None
         self.impl = sac.SAC(self.env, scfg, seed=self.seed)
+        self._mark_fused()
         self._det = self.impl.agent.deterministic_policy()  # one object: evaluate() caches its captured graph per policy object
 
     def _act_module(self):
@@ -294,18 +332,20 @@ class SAC(HipController):
         self.impl.load(path, training=self.training)
 
 
-class DDPG(HipController):
+class DDPG(_OffPolicy):
     """controllers/ddpg/ddpg.py:28-341."""
     DEFAULTS = DDPG_DEFAULTS
+    KIND = 'ddpg'
 
     def _build(self):
         from safe_control_gym_amd import ddpg
         self.activation = self.algo_config.setdefault('activation', 'relu')        # (ddpg.yaml has no such key: DDPGAgent's default)
         dcfg = ddpg.DDPGConfig.from_dict(self.algo_config)
         n = self.rollout_batch_size if self.training else self.eval_batch_size
-        self.env = self._vec(n, self.seed)
+        self.env = self._vec(n, self.seed, self._policy_shape())
         self.eval_env = None
         self.impl = ddpg.DDPG(self.env, dcfg, seed=self.seed)
+        self._mark_fused()
         self._det = self.impl.agent.deterministic_policy()
 
     def reset(self):

@@ -359,3 +359,7 @@ extern "C" int scg_rollout_cbf(scg_env* env, const scg_actor_ptrs* actor, const 
     return fail(SCG_ERR_INVALID, "the CBF filter serves float32 cartpole envs");
 #endif
 }
+
+// ---- the filter behind the SAC / DDPG actor (scg_rollout_cbf_actor) ---------------------------------------------------------------
+#include "scg_actor_rollout.h"
+#include "scg_cbf_actor.h"

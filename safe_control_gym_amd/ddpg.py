@@ -264,6 +264,18 @@ class DDPGAgent:
                 'actor': lay(0), 'q': lay(6), 'low': [float(x) for x in low], 'high': [float(x) for x in high],
                 'counter': torch.zeros(1, dtype=torch.int32, device=dev), 'seed': int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF}
 
+    def actor_struct(self):
+        """The scg_actor (_lib.Actor, include/scg_actor_rollout.h) of the deterministic actor for the fused rollout (HipVecEnv.rollout_actor):
+        the flat vector's actor layout and the bounds cached for scg_ddpg_act.  Fused agents only."""
+        from safe_control_gym_amd import _lib as L
+        if not self.use_fused:
+            raise L.ScgError('actor_struct needs the fused agent (the flat parameter vector)')
+        fl, lay = self._flat, self._flat['actor']
+        pad = [0.0] * (4 - self.act_dim)
+        return L.Actor(d_params=fl['p'].data_ptr(), W1=lay.W1, b1=lay.b1, W2=lay.W2, b2=lay.b2, W3=lay.W3, b3=lay.b3, hidden=self.cfg.hidden_dim,
+                       activation=L.POLICY_ACTS[self.cfg.activation], kind=L.ACTOR_KINDS['ddpg'],
+                       act_low=(L.C.c_float * 4)(*(fl['low'] + pad)), act_high=(L.C.c_float * 4)(*(fl['high'] + pad)))
+
     def act_bounds(self):
         import ctypes as C
         fl = self._flat
@@ -494,6 +506,8 @@ class DDPG:
         # fused collector (scg_ddpg_noisy_act + the env kernel + scg_ddpg_push, replayed as one HIP graph per phase): the fused agent and
         # no running normalisers; extra['fused_collect'] = False keeps the PyTorch collector with the host-side noise process
         self._fused_collect = bool(self.agent.use_fused and not self._normalise and cfg.extra.get('fused_collect', True))
+        # evaluation as ONE scg_rollout_actor launch: set by the controller's extension key `fused_rollout` (controllers.DDPG)
+        self._fused_rollout = False
         self._graph_collect = self.device.type == 'cuda' and bool(cfg.extra.get('graph_collect', cfg.extra.get('cuda_graphs', True)))
         self._collect_graphs = {}
         self.noise_process = None
@@ -507,6 +521,10 @@ class DDPG:
     def uniform_action(self):
         """The warm-up's action_space.sample() per env (ddpg.py:276-277), for the PyTorch collector."""
         return self.low + (self.high - self.low) * torch.rand(self.N, self.act_dim, device=self.device)
+
+    def _policy_struct(self, deterministic=True):
+        """The actor for the fused evaluation (ppo.evaluate(policy=)): deterministic only."""
+        return self.agent.actor_struct()
 
     def reset_noise(self):
         """noise_process.reset_states() of the reference's DDPG.reset() in training mode (ddpg.py:100-102)."""

@@ -1009,8 +1009,13 @@ def _evaluate_fused_device(env, policy, episodes_per_env=1, chunk=None):
     env.reset_tensors()
     buf['acc'].zero_()
     chunk = steps if not chunk else max(1, min(int(chunk), steps))
+    from safe_control_gym_amd import _lib as L
     for t0 in range(0, steps, chunk):
         k = min(chunk, steps - t0)
+        if isinstance(policy, L.Actor):             # a deterministic SAC / DDPG actor (scg_rollout_actor): no log-probabilities
+            env.rollout_actor(policy, k, buf['obs'][t0:t0 + k + 1], buf['act'][t0:t0 + k], buf['rew'][t0:t0 + k], buf['done'][t0:t0 + k],
+                              buf['flags'][t0:t0 + k], episode_acc=buf['acc'], max_episodes=episodes_per_env)
+            continue
         env.rollout_policy(policy, k, buf['obs'][t0:t0 + k + 1], buf['act'][t0:t0 + k], buf['logp'][t0:t0 + k], buf['rew'][t0:t0 + k],
                            buf['done'][t0:t0 + k], buf['flags'][t0:t0 + k], episode_acc=buf['acc'], max_episodes=episodes_per_env)
     a = buf['acc']
@@ -1038,9 +1043,14 @@ def _evaluate_cbf_device(env, policy, safety_filter, episodes_per_env=1):
         env._eval_cbf = buf
     env.reset_tensors()
     buf['acc'].zero_()
-    env.rollout_cbf(_cbf.actor_ptrs_of_policy(policy), safety_filter.params(), steps, buf['obs'], buf['act'], buf['logp'], buf['rew'],
-                    buf['done'], buf['flags'], buf['rows'], buf['applied'], deterministic=True, episode_acc=buf['acc'],
-                    max_episodes=episodes_per_env)
+    from safe_control_gym_amd import _lib as L
+    if isinstance(policy, L.Actor):                 # a deterministic SAC / DDPG actor (scg_rollout_cbf_actor)
+        env.rollout_cbf_actor(policy, safety_filter.params(), steps, buf['obs'], buf['act'], buf['rew'], buf['done'], buf['flags'],
+                              buf['rows'], buf['applied'], episode_acc=buf['acc'], max_episodes=episodes_per_env)
+    else:
+        env.rollout_cbf(_cbf.actor_ptrs_of_policy(policy), safety_filter.params(), steps, buf['obs'], buf['act'], buf['logp'], buf['rew'],
+                        buf['done'], buf['flags'], buf['rows'], buf['applied'], deterministic=True, episode_acc=buf['acc'],
+                        max_episodes=episodes_per_env)
     a = buf['acc']
     n = a[:, 0].sum().clamp(min=1.0)
     res = torch.stack([a[:, 0].sum(), a[:, 1].sum() / n, a[:, 2].sum() / n, a[:, 3].sum() / n, a[:, 4].sum() / n])
@@ -1123,7 +1133,8 @@ def evaluate(ac, env, episodes_per_env=1, use_graph=None, obs_normalizer=None, p
     PPO.run, ppo.py:210-257).  An episode lasts at most CTRL_STEPS control steps, so the loop has a fixed length and no
     host synchronisation; on a GPU it is captured once per (policy, env) pair and replayed as one HIP graph.
     policy: an _lib.Policy with deterministic = 1 (PPO._policy_struct(True)) for an env built with that policy shape —
-    the whole evaluation is then ONE launch of the fused rollout kernel.
+    the whole evaluation is then ONE launch of the fused rollout kernel; or an _lib.Actor (SACAgent / DDPGAgent.actor_struct()) for an
+    env built with policy=(hidden, activation, 'sac' | 'ddpg'): ONE launch of scg_rollout_actor (scg_rollout_cbf_actor with the filter).
     safety_filter: a cbf.CBF — every action passes through the filter before the env step (experiments/base_experiment.py:177-184), as
     ONE launch of scg_rollout_cbf on an env built with policy= and cbf=True; the result gains `safety_filter_data`.  There is no
     unfused filtered evaluation: without such an env (or without `policy`, or with an observation normaliser) this raises."""

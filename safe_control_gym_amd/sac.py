@@ -433,6 +433,19 @@ class SACAgent:
                                         C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         return out
 
+    def actor_struct(self):
+        """The scg_actor (_lib.Actor, include/scg_actor_rollout.h) of the deterministic actor for the fused rollout (HipVecEnv.rollout_actor):
+        the flat vector's actor layout — W3 / b3 the stacked head, whose first act_dim rows are the mean's — and the bounds cached for
+        scg_sac_act.  Fused agents only."""
+        from safe_control_gym_amd import _lib as L
+        if not self.use_fused:
+            raise L.ScgError('actor_struct needs the fused agent (the flat parameter vector)')
+        fl, lay = self._flat, self._flat['actor']
+        pad = [0.0] * (4 - self.act_dim)
+        return L.Actor(d_params=fl['p'].data_ptr(), W1=lay.W1, b1=lay.b1, W2=lay.W2, b2=lay.b2, W3=lay.W3, b3=lay.b3, hidden=self.cfg.hidden_dim,
+                       activation=L.POLICY_ACTS[self.cfg.activation], kind=L.ACTOR_KINDS['sac'],
+                       act_low=(L.C.c_float * 4)(*(fl['low'] + pad)), act_high=(L.C.c_float * 4)(*(fl['high'] + pad)))
+
     def deterministic_policy(self):
         """An object with `.act(obs)` for ppo.evaluate / the controllers (one per agent: evaluate caches its captured graph per policy object)."""
         if getattr(self, '_det_policy', None) is None:
@@ -611,9 +624,15 @@ class SAC:
         # of ~40 PyTorch kernels per vector step.  Needs the fused agent and no running normalisers; extra['fused_collect'] = False
         # keeps the PyTorch collector (A/B, tests) — chosen here, visibly.
         self._fused_collect = bool(self.agent.use_fused and not self._normalise and cfg.extra.get('fused_collect', True))
+        # evaluation as ONE scg_rollout_actor launch: set by the controller's extension key `fused_rollout` (controllers.SAC)
+        self._fused_rollout = False
         if self._fused_collect:
             self._act = torch.zeros(self.N, self.act_dim, device=self.device)
             self._collect_counter = torch.zeros(1, dtype=torch.int32, device=self.device)       # counter word of the action noise
+
+    def _policy_struct(self, deterministic=True):
+        """The actor for the fused evaluation (ppo.evaluate(policy=)): deterministic only."""
+        return self.agent.actor_struct()
 
     # ---- one vectorised env step into the replay ring (sac.py:273-311)
     @torch.no_grad()

@@ -227,10 +227,17 @@ class HipVecEnv(VecEnv):
         # config-specialised library when one was built for this config (specialize=True compiles it now)
         # policy=(hidden, activation): use the variant of the specialised library that also carries the fused
         # policy-in-the-loop rollout kernel for that actor shape (rollout_policy below); float32 only
+        # policy=(hidden, activation, 'sac' | 'ddpg'): the variant that carries the deterministic SAC / DDPG actor's rollout as well
+        # (rollout_actor below); the tuple is checked before anything is built
         self.policy_shape = None
+        if policy is not None and len(policy) != 2:
+            policy = L.policy_tuple(policy)
         if policy is not None and dtype == torch.float32 and L.policy_supported(self.spec.obs_dim, int(policy[0]), self.spec.nu, policy[1]) \
                 and self.spec.obs_dim in (self.spec.nx, 2 * self.spec.nx):
-            self.policy_shape = (int(policy[0]), policy[1])
+            self.policy_shape = (int(policy[0]), policy[1]) + tuple(policy[2:])
+        self.actor_kind = self.policy_shape[2] if self.policy_shape is not None and len(self.policy_shape) == 3 else None
+        if policy is not None and len(policy) == 3 and (adversaries is not None or safety_layer is not None):
+            raise ValueError("a policy kind ('sac' | 'ddpg') cannot be combined with adversaries= or safety_layer=")
         # adversaries=n (with policy=): the library that also carries the RARL / RAP collector (rollout_adversarial below) for the
         # protagonist's shape and n adversaries of the same shape; a shape it cannot serve leaves adversary_shape None
         self.adversary_shape = None
@@ -264,7 +271,10 @@ class HipVecEnv(VecEnv):
                 raise ValueError('cbf=True cannot be combined with adversaries= or safety_layer=')
             if env_id != 'cartpole':
                 raise NotImplementedError('[Error] Currently CBF is only implemented for the cartpole system.')
-            if self.policy_shape is None or not _cbf.supported(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1]):
+            served = self.policy_shape is not None and (
+                _cbf.supported(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1]) if self.actor_kind is None
+                else _cbf.supported_actor(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1], self.actor_kind))
+            if not served:
                 raise L.ScgError('cbf=True needs a float32 env and policy=(hidden, activation) of a shape the fused policy rollout serves')
             self.cbf_shape = self.policy_shape
         # ilqr=True: the library that also carries the LQR / iLQR controllers' kernels (rollout_feedback / ilqr_backward below)
@@ -434,6 +444,40 @@ class HipVecEnv(VecEnv):
         o.max_episodes = int(max_episodes)
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_policy(self._h, C.byref(policy), int(k_steps), C.byref(o), self._stream()))
+
+    def _actor_rollout_out(self, obs, act, reward, done, flags, terminal_obs, episode_acc, max_episodes):
+        o = L.PolicyRollout()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        o.d_obs, o.d_act, o.d_logp, o.d_reward, o.d_done, o.d_flags = p(obs), p(act), None, p(reward), p(done), p(flags)
+        o.d_terminal_obs, o.d_ep_stats, o.d_episode_acc = p(terminal_obs), p(self.ep_stats), p(episode_acc)
+        o.max_episodes = int(max_episodes)
+        return o
+
+    def rollout_actor(self, actor, k_steps, obs, act, reward, done, flags, terminal_obs=None, episode_acc=None, max_episodes=0):
+        """K control steps in ONE launch with the deterministic SAC / DDPG actor in the loop (scg_rollout_actor): `actor` is an
+        _lib.Actor (SACAgent.actor_struct() / DDPGAgent.actor_struct()), the other arguments are rollout_policy's without logp."""
+        if self.actor_kind is None:
+            raise L.ScgError("this env was not built with an actor kind (HipVecEnv(..., policy=(hidden, activation, 'sac' | 'ddpg')))")
+        o = self._actor_rollout_out(obs, act, reward, done, flags, terminal_obs, episode_acc, max_episodes)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_actor(self._h, C.byref(actor), int(k_steps), C.byref(o), self._stream()))
+
+    def rollout_cbf_actor(self, actor, params, k_steps, obs, act, reward, done, flags, filter_rows, applied, terminal_obs=None,
+                          episode_acc=None, max_episodes=0):
+        """rollout_actor with the CBF filter between the actor and the env step (scg_rollout_cbf_actor): `params` an _cbf.CbfParams;
+        filter_rows [K, N, 4] and applied [K, N] as for rollout_cbf; act keeps the actor's own action."""
+        if self.cbf_shape is None or self.actor_kind is None:
+            raise L.ScgError("this env was not built with the CBF filter behind an actor kind (HipVecEnv(..., policy=(hidden, activation, "
+                             "'sac' | 'ddpg'), cbf=True))")
+        if filter_rows.shape != (int(k_steps), self.num_envs, 4) or applied.shape != (int(k_steps), self.num_envs):
+            raise ValueError(f'filter_rows must be [{int(k_steps)}, {self.num_envs}, 4] and applied [{int(k_steps)}, {self.num_envs}]')
+        for t in (filter_rows, applied):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('filter_rows and applied must be contiguous float32 tensors on the env device')
+        o = self._actor_rollout_out(obs, act, reward, done, flags, terminal_obs, episode_acc, max_episodes)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_cbf_actor(self._h, C.byref(actor), C.byref(params), int(k_steps), C.byref(o),
+                                                      C.c_void_p(filter_rows.data_ptr()), C.c_void_p(applied.data_ptr()), self._stream()))
 
     def rollout_adversarial(self, policy, adversaries, k_steps, obs, act, logp, reward, done, flags, adv_act, adv_logp, adv_index=None,
                             deterministic_adversary=False, terminal_obs=None, episode_acc=None, max_episodes=0):
