@@ -5,9 +5,9 @@ No fallback lives here: callers that cannot get a library for their shape (hidde
 action dimensions, unknown activation) use the PyTorch update path explicitly (ppo.py decides, and says so)."""
 import ctypes as C
 import os
-import subprocess
 
 from safe_control_gym_amd import _lib as L
+from safe_control_gym_amd import _shapelib
 
 ACTS = {'tanh': 0, 'relu': 1, 'leaky_relu': 2}
 SRC = os.path.join(L.CSRC_DIR, 'scg_learn.hip')
@@ -32,12 +32,7 @@ def supported(obs_dim, hidden, act_dim, activation):
 
 
 def source_hash():
-    import hashlib
-    h = hashlib.sha256()
-    for p in DEPS:
-        with open(p, 'rb') as f:
-            h.update(os.path.basename(p).encode() + b'\0' + f.read())
-    return int.from_bytes(h.digest()[:8], 'little')
+    return _shapelib.source_hash(DEPS)
 
 
 def lib_path(obs_dim, hidden, act_dim, activation):
@@ -49,33 +44,11 @@ def lib_path(obs_dim, hidden, act_dim, activation):
 def build(obs_dim, hidden, act_dim, activation, force=False):
     if not supported(obs_dim, hidden, act_dim, activation):
         raise L.ScgError(f'no MFMA learner for obs {obs_dim} hidden {hidden} act {act_dim} {activation}')
-    so = lib_path(obs_dim, hidden, act_dim, activation)
-    if not force and os.path.exists(so) and L._lib_source_hash(so) == source_hash():
-        return so
-    os.makedirs(L.SPEC_DIR, exist_ok=True)
-    cmd = [L._hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', f'-DSCG_L_NIN={obs_dim}',
-           f'-DSCG_L_H={hidden}', f'-DSCG_L_NU={act_dim}', f'-DSCG_L_ACT={ACTS[activation]}',
-           f'-DSCG_SRC_HASH=0x{source_hash():016x}ULL', '-o', so, SRC] + os.environ.get('SCG_LEARN_FLAGS', '').split()
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if res.returncode != 0:
-        raise L.ScgError('hipcc failed (learner build):\n' + res.stdout + res.stderr)
-    return so
+    defines = {'SCG_L_NIN': obs_dim, 'SCG_L_H': hidden, 'SCG_L_NU': act_dim, 'SCG_L_ACT': ACTS[activation]}
+    return _shapelib.build(lib_path(obs_dim, hidden, act_dim, activation), SRC, DEPS, defines, 'learner', 'SCG_LEARN_FLAGS', force)
 
 
-_libs = {}
-
-
-def lib(obs_dim, hidden, act_dim, activation):
-    """The learner library of this shape: in-tree build when present and current, compiled now when hipcc is available."""
-    key = (obs_dim, hidden, act_dim, activation)
-    if key in _libs:
-        return _libs[key]
-    so = lib_path(*key)
-    if not os.path.exists(so) or L._lib_source_hash(so) != source_hash():
-        if not os.path.exists(L._hipcc()):
-            raise L.ScgError(f'{so} is missing or stale and hipcc is not available to build it')
-        build(*key, force=True)
-    D = C.CDLL(so)
+def _bind(D):
     D.scg_learn_last_error.restype = C.c_char_p
     D.scg_ppo_grad_workspace_bytes.restype = C.c_size_t
     D.scg_ppo_grad_workspace_bytes.argtypes = [C.c_int]
@@ -94,12 +67,16 @@ def lib(obs_dim, hidden, act_dim, activation):
     D.scg_ppo_returns_scratch_bytes.restype = C.c_size_t
     D.scg_ppo_returns_moments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     D.scg_ppo_returns_normalise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    shape = [C.c_int32() for _ in range(4)]
-    D.scg_learn_shape(*[C.byref(v) for v in shape])
-    if tuple(v.value for v in shape) != (obs_dim, hidden, act_dim, ACTS[activation]):
-        raise L.ScgError(f'{so} was built for another network shape')
-    _libs[key] = D
-    return D
+
+
+_libs = {}
+
+
+def lib(obs_dim, hidden, act_dim, activation):
+    """The learner library of this shape: in-tree build when present and current, compiled now when hipcc is available."""
+    key = (obs_dim, hidden, act_dim, activation)
+    return _shapelib.load(_libs, key, lib_path(*key), DEPS, lambda: build(*key, force=True), _bind, 'scg_learn_shape',
+                          (obs_dim, hidden, act_dim, ACTS[activation]))
 
 
 def check(D, rc):

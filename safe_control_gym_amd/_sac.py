@@ -3,15 +3,14 @@ of SACAgent.update on the matrix cores, compiled per network shape from csrc/scg
 GPU; ~8 s).  No fallback lives here: sac.py uses the PyTorch update, visibly, for shapes this library does not serve."""
 import ctypes as C
 import os
-import subprocess
 
 from safe_control_gym_amd import _lib as L
+from safe_control_gym_amd import _shapelib
 from safe_control_gym_amd._learn import ACTS, MlpLayout
 
 SRC = os.path.join(L.CSRC_DIR, 'scg_sac.hip')
-DEPS = [SRC, os.path.join(L.CSRC_DIR, 'scg_adam.h'), os.path.join(L.CSRC_DIR, 'scg_mlp.h'), os.path.join(L.CSRC_DIR, 'scg_once.h'), os.path.join(L.CSRC_DIR, 'scg_rng.h'),
-        os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_sac.h')),
-        os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_learn.h'))]
+DEPS = [SRC] + [os.path.join(L.CSRC_DIR, h) for h in ('scg_wide.h', 'scg_adam.h', 'scg_mlp.h', 'scg_once.h', 'scg_rng.h')] + \
+    [os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', h)) for h in ('scg_sac.h', 'scg_learn.h')]
 
 
 class SacArgs(C.Structure):
@@ -39,12 +38,7 @@ def supported(obs_dim, hidden, act_dim, activation):
 
 
 def source_hash():
-    import hashlib
-    h = hashlib.sha256()
-    for p in DEPS:
-        with open(p, 'rb') as f:
-            h.update(os.path.basename(p).encode() + b'\0' + f.read())
-    return int.from_bytes(h.digest()[:8], 'little')
+    return _shapelib.source_hash(DEPS)
 
 
 def lib_path(obs_dim, hidden, act_dim, activation):
@@ -54,32 +48,11 @@ def lib_path(obs_dim, hidden, act_dim, activation):
 def build(obs_dim, hidden, act_dim, activation, force=False):
     if not supported(obs_dim, hidden, act_dim, activation):
         raise L.ScgError(f'no fused SAC update for obs {obs_dim} hidden {hidden} act {act_dim} {activation}')
-    so = lib_path(obs_dim, hidden, act_dim, activation)
-    if not force and os.path.exists(so) and L._lib_source_hash(so) == source_hash():
-        return so
-    os.makedirs(L.SPEC_DIR, exist_ok=True)
-    cmd = [L._hipcc(), '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', f'-DSCG_S_NOBS={obs_dim}', f'-DSCG_S_H={hidden}',
-           f'-DSCG_S_NU={act_dim}', f'-DSCG_S_ACT={ACTS[activation]}', f'-DSCG_SRC_HASH=0x{source_hash():016x}ULL', '-o', so, SRC] \
-        + os.environ.get('SCG_SAC_FLAGS', '').split()
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if res.returncode != 0:
-        raise L.ScgError('hipcc failed (SAC build):\n' + res.stdout + res.stderr)
-    return so
+    defines = {'SCG_S_NOBS': obs_dim, 'SCG_S_H': hidden, 'SCG_S_NU': act_dim, 'SCG_S_ACT': ACTS[activation]}
+    return _shapelib.build(lib_path(obs_dim, hidden, act_dim, activation), SRC, DEPS, defines, 'SAC', 'SCG_SAC_FLAGS', force)
 
 
-_libs = {}
-
-
-def lib(obs_dim, hidden, act_dim, activation):
-    key = (obs_dim, hidden, act_dim, activation)
-    if key in _libs:
-        return _libs[key]
-    so = lib_path(*key)
-    if not os.path.exists(so) or L._lib_source_hash(so) != source_hash():
-        if not os.path.exists(L._hipcc()):
-            raise L.ScgError(f'{so} is missing or stale and hipcc is not available to build it')
-        build(*key, force=True)
-    D = C.CDLL(so)
+def _bind(D):
     D.scg_sac_last_error.restype = C.c_char_p
     D.scg_sac_workspace_bytes.restype = C.c_size_t
     D.scg_sac_workspace_bytes.argtypes = [C.c_int]
@@ -90,12 +63,15 @@ def lib(obs_dim, hidden, act_dim, activation):
     D.scg_sac_sample.argtypes = [C.c_void_p, C.POINTER(MlpLayout), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int, C.c_uint64,
                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     D.scg_sac_push.argtypes = [C.POINTER(SacRing), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    shape = [C.c_int32() for _ in range(4)]
-    D.scg_sac_shape(*[C.byref(v) for v in shape])
-    if tuple(v.value for v in shape) != (obs_dim, hidden, act_dim, ACTS[activation]):
-        raise L.ScgError(f'{so} was built for another network shape')
-    _libs[key] = D
-    return D
+
+
+_libs = {}
+
+
+def lib(obs_dim, hidden, act_dim, activation):
+    key = (obs_dim, hidden, act_dim, activation)
+    return _shapelib.load(_libs, key, lib_path(*key), DEPS, lambda: build(*key, force=True), _bind, 'scg_sac_shape',
+                          (obs_dim, hidden, act_dim, ACTS[activation]))
 
 
 def check(D, rc):

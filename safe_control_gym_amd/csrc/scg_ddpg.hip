@@ -308,21 +308,7 @@ __global__ __launch_bounds__(64 * NT, 1) void actor_grad_kernel(const float* __r
 }  // namespace wide
 }  // namespace scg
 
-// Sum of the workgroups' partials -> flat gradient (torch parameter order) of one network.
-template <int NIN, int NOUT>
-__device__ __forceinline__ int dest_of(int k, const scg_mlp_layout& lay) {
-    using G = Part<NIN, NOUT>;
-    if (k < G::DB2) { const int in = k / HID, o = k % HID; return in < NIN ? lay.W1 + o * NIN + in : lay.b1 + o; }
-    if (k < G::DW3) return lay.b2 + (k - G::DB2);
-    if (k < G::DB3) return lay.W3 + (k - G::DW3);
-    if (k < G::STAT) return (k - G::DB3) < NOUT ? lay.b3 + (k - G::DB3) : -1;
-    if (k < G::DW2) return -2 - (k - G::STAT);
-    const int p = k - G::DW2;                               // [tile][g][lane][4]
-    const int q = 4 * ((p >> 8) & 3) + (p & 3), lane = (p >> 2) & 63, tr = p >> 10;
-    const int tau = tr / NT, rho = tr % NT;
-    return lay.W2 + (32 * rho + (lane & 31)) * HID + 32 * tau + d_row(q, lane >> 5);
-}
-
+// Sum of the workgroups' partials -> flat gradient (torch parameter order: dest_of, scg_wide.h) of one network.
 // Each parameter is written by exactly one thread of one launch: its sum over the partials (four groups of every fourth partial,
 // then a fixed pairing), its torch.optim.Adam step and its soft update.  The step's bookkeeping rides here as well, every word
 // touched by one thread of a launch in which nobody else reads it:
@@ -546,41 +532,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void noisy_act_kernel(const float* _
     }
 }
 
-// warm-up actions: action_space.sample() per env, a ~ U[low, high) per dimension
-__global__ __launch_bounds__(256) void uniform_action_kernel(int m, float4 low, float4 high, uint32_t k0, uint32_t k1,
-                                                              const uint32_t* __restrict__ counter, int32_t* __restrict__ pending,
-                                                              float* __restrict__ a_out) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (pending && s == 0) *pending = 0;
-    if (s >= m) return;
-    const float lo[4] = {low.x, low.y, low.z, low.w}, hi[4] = {high.x, high.y, high.z, high.w};
-    const U4 w = philox4x32_10(U4{counter ? *counter : 0u, (uint32_t)s, 4u, 0x5ac1u}, k0, k1);
-    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int j = 0; j < NU; ++j) a_out[(size_t)s * NU + j] = lo[j] + (hi[j] - lo[j]) * u01<float>(ww[j]);
-}
-
-// One vectorised env step into the replay ring (the time-limit fix-up of ddpg.py:293-311, as sac.py's): one thread per (env, element)
-struct RingArgs {
-    float* obs; float* act; float* rew; float* next_obs; float* mask; int capacity;
-    long long* pos; float* size_f; int32_t* size_i; uint32_t* counter;
-};
-__global__ __launch_bounds__(256) void ring_push_kernel(const RingArgs R, float* __restrict__ cur_obs, const float* __restrict__ act,
-                                                         const float* __restrict__ rew, const float* __restrict__ next,
-                                                         const float* __restrict__ term, const uint8_t* __restrict__ done,
-                                                         const uint8_t* __restrict__ flags, int n) {
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= n * NOBS) return;
-    const int i = gid / NOBS, e = gid - i * NOBS;
-    const size_t slot = (size_t)((*R.pos + i) % R.capacity);
-    const bool dn = done[i] != 0, trunc = dn && (flags[i] & 1);
-    const float nv = next[gid];
-    R.obs[slot * NOBS + e] = cur_obs[gid];
-    R.next_obs[slot * NOBS + e] = trunc ? term[gid] : nv;
-    cur_obs[gid] = nv;
-    for (int j = e; j < NU; j += NOBS) R.act[slot * NU + j] = act[(size_t)i * NU + j];     // every action column, also when NOBS < NU
-    if (e == 0) { R.rew[slot] = rew[i]; R.mask[slot] = trunc ? 1.0f : (dn ? 0.0f : 1.0f); }
-}
+// (uniform_action_kernel, RingArgs and ring_push_kernel: scg_wide.h.)  Behind a push: the ring's write position and the commit of the
+// exploration noise the step's actions drew, one thread.
 struct CommitArgs { double* x_prev; const double* x_next; int64_t* calls; int32_t* pending; int kind; };
 __global__ void bookkeeping_kernel(const RingArgs R, int with_ring, int n, const CommitArgs Cn) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;

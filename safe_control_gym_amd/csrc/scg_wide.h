@@ -1,7 +1,9 @@
-// scg_wide.h — the wide-tile MLP passes of the fused off-policy gradient steps, for libraries other than libscg_sac_*: the
-// helpers below are re-expressed from scg_sac.hip (which keeps its own copy: its bytes feed the SAC library's source hash).
+// scg_wide.h — the wide-tile MLP passes of the fused off-policy gradient steps, and the collector kernels the off-policy agents
+// share: the one home of the scheme, included by libscg_sac_* (scg_sac.hip) and libscg_ddpg_* (scg_ddpg.hip).  What differs between
+// the algorithms — the step's kernels (two critics and a temperature against one critic), the loss heads, the host side — stays in
+// the two .hip files; an edit here makes both libraries stale (_sac.DEPS, _ddpg.DEPS).
 // Include AFTER defining the network constants: NOBS, HID, NU, ACT, NQ (= NOBS + NU), NA (actor head width), NT (= HID / 32),
-// and SCG_S_STAMP (a no-op outside timing builds).
+// and SCG_S_STAMP (a no-op outside scg_sac.hip's timing builds).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -503,5 +505,63 @@ __device__ __forceinline__ void act_load(const float* __restrict__ base, int til
     }
 }
 }  // namespace wide
+
+// Word k of a partial vector (Part<NIN, NOUT>) -> its element of the flat gradient (torch parameter order); -1: padding,
+// -2 - j: statistics word j.  The reduction launches sum the workgroups' partials through it.
+template <int NIN, int NOUT>
+__device__ __forceinline__ int dest_of(int k, const scg_mlp_layout& lay) {
+    using G = Part<NIN, NOUT>;
+    if (k < G::DB2) { const int in = k / HID, o = k % HID; return in < NIN ? lay.W1 + o * NIN + in : lay.b1 + o; }
+    if (k < G::DW3) return lay.b2 + (k - G::DB2);
+    if (k < G::DB3) return lay.W3 + (k - G::DW3);
+    if (k < G::STAT) return (k - G::DB3) < NOUT ? lay.b3 + (k - G::DB3) : -1;
+    if (k < G::DW2) return -2 - (k - G::STAT);
+    const int p = k - G::DW2;                               // [tile][g][lane][4]
+    const int q = 4 * ((p >> 8) & 3) + (p & 3), lane = (p >> 2) & 63, tr = p >> 10;
+    const int tau = tr / NT, rho = tr % NT;
+    return lay.W2 + (32 * rho + (lane & 31)) * HID + 32 * tau + d_row(q, lane >> 5);
+}
+
+// ================================================================== collector (the agents' env-facing half)
+// warm-up actions: action_space.sample() per env (sac.py:276-277), a ~ U[low, high) per dimension.  `pending` (nullable): DDPG's count
+// of envs whose exploration noise awaits its commit — a uniform action draws none.
+__global__ __launch_bounds__(256) void uniform_action_kernel(int m, float4 low, float4 high, uint32_t k0, uint32_t k1,
+                                                              const uint32_t* __restrict__ counter, int32_t* __restrict__ pending,
+                                                              float* __restrict__ a_out) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pending && s == 0) *pending = 0;
+    if (s >= m) return;
+    const float lo[4] = {low.x, low.y, low.z, low.w}, hi[4] = {high.x, high.y, high.z, high.w};
+    const U4 w = philox4x32_10(U4{counter ? *counter : 0u, (uint32_t)s, 4u, 0x5ac1u}, k0, k1);
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int j = 0; j < NU; ++j) a_out[(size_t)s * NU + j] = lo[j] + (hi[j] - lo[j]) * u01<float>(ww[j]);
+}
+
+// One vectorised env step into the replay ring (SACBuffer.push with the time-limit fix-up of sac.py:287-305, ddpg.py:293-311): row
+// pos + i (mod capacity) <- (obs the action was taken at, action, reward, next observation — the TERMINAL observation where the episode
+// was truncated by the time limit —, mask = 1 if truncated else 1 - done); the persistent current-observation batch becomes the
+// step's observation.  One thread per (env, observation element).  The write position is read here by everybody and advanced by the
+// one-thread launch behind it (scg_sac.hip: ring_advance_kernel; scg_ddpg.hip: bookkeeping_kernel, with the noise commit).
+struct RingArgs {
+    float* obs; float* act; float* rew; float* next_obs; float* mask; int capacity;
+    long long* pos; float* size_f; int32_t* size_i; uint32_t* counter;
+};
+__global__ __launch_bounds__(256) void ring_push_kernel(const RingArgs R, float* __restrict__ cur_obs, const float* __restrict__ act,
+                                                         const float* __restrict__ rew, const float* __restrict__ next,
+                                                         const float* __restrict__ term, const uint8_t* __restrict__ done,
+                                                         const uint8_t* __restrict__ flags, int n) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= n * NOBS) return;
+    const int i = gid / NOBS, e = gid - i * NOBS;
+    const size_t slot = (size_t)((*R.pos + i) % R.capacity);
+    const bool dn = done[i] != 0, trunc = dn && (flags[i] & 1);
+    const float nv = next[gid];
+    R.obs[slot * NOBS + e] = cur_obs[gid];
+    R.next_obs[slot * NOBS + e] = trunc ? term[gid] : nv;
+    cur_obs[gid] = nv;
+    for (int j = e; j < NU; j += NOBS) R.act[slot * NU + j] = act[(size_t)i * NU + j];     // every action column, also when NOBS < NU
+    if (e == 0) { R.rew[slot] = rew[i]; R.mask[slot] = trunc ? 1.0f : (dn ? 0.0f : 1.0f); }
+}
 
 }  // namespace scg

@@ -1,5 +1,5 @@
-"""Host model of the off-policy collectors' in-kernel random draws (csrc/scg_sac.hip / csrc/scg_wide.h `normal4`, the two
-`uniform_action_kernel`s), in float64 on top of oracle/rng.py's Philox4x32-10.
+"""Host model of the off-policy collectors' in-kernel random draws (csrc/scg_wide.h: `normal4` and
+`uniform_action_kernel`, one definition for the SAC and the DDPG library), in float64 on top of oracle/rng.py's Philox4x32-10.
 
     key     = (seed & 0xffffffff, seed >> 32)
     counter = (*d_counter, row, stream, 0x5ac1)          stream 3: the collector's N(0, 1) draws, 4: the uniform warm-up action

@@ -537,8 +537,8 @@ def test_ddpg_uniform_warm_up(shape):
 def test_in_kernel_draw_readout():
     """The in-kernel N(0, 1) draw read out directly: Gaussian noise of std 2^20 swamps the action, so (a - a64) / 2^20 is the kernel's
     eps to ~1e-7.  Checks |eps_kernel - eps64| <= D_EPS (1 + |eps|) + D_LOG / r and prints the two constants' measured counterparts:
-    max |d eps| r where r < 0.05 (the __logf term) and max |d eps| / (1 + |eps|) where r >= 0.05.  scg_sac.hip's normal4 is the same
-    function (scg_wide.h), pinned within the same allowance through test_sac_sample_in_kernel_draw."""
+    max |d eps| r where r < 0.05 (the __logf term) and max |d eps| / (1 + |eps|) where r >= 0.05.  The SAC library compiles the same
+    normal4 (scg_wide.h holds the one definition), pinned within the same allowance through test_sac_sample_in_kernel_draw."""
     shape = (24, 128, 4, 'relu')
     ag, D = ddpg_agent(shape)
     B = Bounds(NARROW, 4)

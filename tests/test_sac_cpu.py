@@ -210,3 +210,25 @@ def test_sac_collector_reproduces_the_reference_buffer(device, norm):
         np.testing.assert_allclose(r.ret.cpu().numpy(), G['norm/ret'], **kw)
         np.testing.assert_allclose(sac.obs.cpu().numpy(), G['final_obs'], rtol=0, atol=1e-6)
         assert np.abs(G['buffer/obs']).max() <= 4.0 + 1e-6 and np.abs(G['buffer/rew']).max() <= 2.0 + 1e-6
+
+
+def test_wide_tile_code_has_one_home_and_every_include_is_hashed():
+    """scg_wide.h is the only definition of the wide-tile passes, and every header the SAC and DDPG libraries include — directly or
+    through it — is in their DEPS, so that editing one makes the libraries stale."""
+    import os
+    import re
+    from safe_control_gym_amd import _ddpg, _sac
+
+    def includes(path):
+        with open(path) as f:
+            return {os.path.normpath(os.path.join(os.path.dirname(path), name)) for name in re.findall(r'#include "([^"]+)"', f.read())}
+    wide = os.path.join(os.path.dirname(_sac.SRC), 'scg_wide.h')
+    for mod in (_sac, _ddpg):
+        deps = {os.path.normpath(p) for p in mod.DEPS}
+        assert wide in includes(mod.SRC)
+        missing = (includes(mod.SRC) | includes(wide)) - deps
+        assert not missing, f'{os.path.basename(mod.SRC)}: not in DEPS: {sorted(missing)}'
+    with open(_sac.SRC) as f:
+        sac = f.read()
+    for definition in ('struct Part', 'store_wt(', 'struct Xch', 'void backward('):
+        assert definition not in sac, f'scg_sac.hip defines {definition!r} again'
