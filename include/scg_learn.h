@@ -105,16 +105,20 @@ void scg_learn_force_accumulating_form(int on);
  *   scg_ppo_returns_prepare    d_trunc = done & (flags & 1) (time truncation is not termination), d_mask = 1 - done, d_rew_out = rew
  *                              (scg_gae adds gamma * terminal_v to it in place), d_v_out = d_v_all[:T]; run it in front of the masked
  *                              critic pass over the terminal observations (scg_mlp_forward with d_row_mask = d_trunc)
- *   scg_ppo_returns_moments    d_moments[3] = {sum adv, sum adv^2, T N} (fixed-order two-stage sum); d_episode_acc (nullable, [N][8]:
- *                              scg_policy_rollout.d_episode_acc): columns 0..3 are added to d_episode_totals[4] and the array is zeroed
+ *   scg_ppo_returns_moments    d_moments[3] = {sum adv, sum adv^2, T N} as DOUBLES, accumulated in float64 from the first add on
+ *                              (fixed-order two-stage sum; d_scratch: scg_ppo_returns_scratch_bytes() bytes; both 8-byte aligned);
+ *                              d_episode_acc (nullable, [N][8]: scg_policy_rollout.d_episode_acc): columns 0..3 are added (in float32)
+ *                              to d_episode_totals[4] and the array is zeroed
  *   scg_ppo_returns_normalise  d_out = (adv - mean) / (std + 1e-6), population std (ppo.py:300), from d_moments — all-reduce (sum) the
- *                              moments between the two calls on several ranks.  d_out may alias d_adv. */
+ *                              three doubles between the two calls on several ranks.  mean, variance and adv - mean are formed in
+ *                              float64 and the quotient is rounded once, on the store: the one-pass variance sum adv^2 / n - mean^2
+ *                              keeps ~8 digits at |mean| / std = 1e4 (in float32 none are left at 1e3).  d_out may alias d_adv. */
 int scg_ppo_returns_prepare(const uint8_t* d_done, const uint8_t* d_flags, const float* d_rew, const float* d_v_all, int T, int N,
                             uint8_t* d_trunc, float* d_mask, float* d_rew_out, float* d_v_out, void* stream);
 size_t scg_ppo_returns_scratch_bytes(void);
-int scg_ppo_returns_moments(const float* d_adv, int T, int N, float* d_episode_acc, float* d_scratch, float* d_moments,
+int scg_ppo_returns_moments(const float* d_adv, int T, int N, float* d_episode_acc, void* d_scratch, double* d_moments,
                             float* d_episode_totals, void* stream);
-int scg_ppo_returns_normalise(const float* d_adv, const float* d_moments, int T, int N, float* d_out, void* stream);
+int scg_ppo_returns_normalise(const float* d_adv, const double* d_moments, int T, int N, float* d_out, void* stream);
 
 /* d_out[i] = pi(i) for i < count, pi a keyed pseudo-random permutation of [0, n) (count <= n): the shuffled row indices of
  * one epoch's minibatches (SubsetRandomSampler + BatchSampler(drop_last=True), ppo_utils.py:358-371), one launch. */

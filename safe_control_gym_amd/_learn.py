@@ -65,6 +65,7 @@ def _bind(D):
     D.scg_ppo_returns_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
     D.scg_ppo_returns_scratch_bytes.restype = C.c_size_t
+    # (d_adv, T, N, d_episode_acc, d_scratch, d_moments: DOUBLE [3], d_episode_totals, stream) / (d_adv, d_moments: DOUBLE [3], T, N, d_out, stream)
     D.scg_ppo_returns_moments.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     D.scg_ppo_returns_normalise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
 

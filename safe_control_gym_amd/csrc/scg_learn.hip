@@ -997,6 +997,10 @@ __global__ __launch_bounds__(256) void permutation_kernel(int32_t* __restrict__ 
 //   moments:    block partials of sum(adv), sum(adv^2) and of the first four columns of the per-env episode accumulators, which are zeroed
 //   finish:     fixed-order sum of the partials -> moments = {sum, sum of squares, count}; the episode totals are added to the running ones
 //   normalise:  adv <- (adv - mean) / (std + 1e-6), population std (ppo.py:300), from the moments (after the caller's all-reduce, if any)
+// The moments are float64 from the first add to the last use: every thread widens its element and accumulates sum and sum of squares (one
+// FMA) in double, the block and finishing sums are double, and normalise forms mean, variance and adv - mean in double and rounds once, on the
+// store.  In float32, sum(adv^2)/n - mean^2 cancels as soon as |mean| is large against std (|mean|/std = 1e3: no digit left); in float64 it
+// keeps ~8 digits at |mean|/std = 1e4.  The launches are bound by the one read of adv, not by the adds.  The episode columns stay float32.
 constexpr int RET_BLOCKS = 256;
 __global__ __launch_bounds__(256) void returns_prepare_kernel(const uint8_t* __restrict__ done, const uint8_t* __restrict__ flags,
                                                                const float* __restrict__ rew, const float* __restrict__ v_all, int M,
@@ -1010,20 +1014,24 @@ __global__ __launch_bounds__(256) void returns_prepare_kernel(const uint8_t* __r
         v_out[i] = v_all[i];
     }
 }
-__device__ __forceinline__ float block_sum256(float v, float* red) {       // fixed order: butterfly inside the wave, waves 0..3 in order
+template <typename T>
+__device__ __forceinline__ T block_sum256(T v, T* red) {                   // fixed order: butterfly inside the wave, waves 0..3 in order
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    const float s = (red[0] + red[1]) + (red[2] + red[3]);
+    const T s = (red[0] + red[1]) + (red[2] + red[3]);
     __syncthreads();
     return s;
 }
+// scratch: [RET_BLOCKS][2] double (sum, sum of squares) followed by [RET_BLOCKS][4] float (episode columns)
 __global__ __launch_bounds__(256) void returns_moments_kernel(const float* __restrict__ adv, int M, float* __restrict__ episode_acc, int N,
-                                                               float* __restrict__ partials) {
+                                                               double* __restrict__ partials, float* __restrict__ ep_partials) {
+    __shared__ double red_d[4];
     __shared__ float red[4];
-    float s1 = 0.0f, s2 = 0.0f, e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) { const float a = adv[i]; s1 += a; s2 = __builtin_fmaf(a, a, s2); }
+    double s1 = 0.0, s2 = 0.0;
+    float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) { const double a = (double)adv[i]; s1 += a; s2 = __builtin_fma(a, a, s2); }
     if (episode_acc) {
         for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
             f32x4* const row = reinterpret_cast<f32x4*>(episode_acc + (size_t)n * 8);
@@ -1032,36 +1040,58 @@ __global__ __launch_bounds__(256) void returns_moments_kernel(const float* __res
             row[0] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f}; row[1] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         }
     }
-    float out[6] = {block_sum256(s1, red), block_sum256(s2, red), block_sum256(e[0], red), block_sum256(e[1], red), block_sum256(e[2], red),
-                    block_sum256(e[3], red)};
+    const double d[2] = {block_sum256(s1, red_d), block_sum256(s2, red_d)};
+    const float out[4] = {block_sum256(e[0], red), block_sum256(e[1], red), block_sum256(e[2], red), block_sum256(e[3], red)};
     if (threadIdx.x == 0) {
+        partials[blockIdx.x * 2 + 0] = d[0]; partials[blockIdx.x * 2 + 1] = d[1];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) partials[blockIdx.x * 8 + k] = out[k];
+        for (int k = 0; k < 4; ++k) ep_partials[blockIdx.x * 4 + k] = out[k];
     }
 }
-__global__ __launch_bounds__(256) void returns_finish_kernel(const float* __restrict__ partials, int n_blocks, float count, float* __restrict__ moments,
-                                                              float* __restrict__ ep_totals) {
+__global__ __launch_bounds__(256) void returns_finish_kernel(const double* __restrict__ partials, const float* __restrict__ ep_partials, int n_blocks,
+                                                              double count, double* __restrict__ moments, float* __restrict__ ep_totals) {
     // thread b holds block b's six partial sums; six fixed-order block sums (one thread walking the 256 partials of a column was 256
     // dependent loads: 32 us)
+    __shared__ double red_d[4];
     __shared__ float red[4];
     const int b = threadIdx.x;
-    float v[6];
+    double v[2];
+    float w[4];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] = b < n_blocks ? partials[b * 8 + k] : 0.0f;
-    float s[6];
+    for (int k = 0; k < 2; ++k) v[k] = b < n_blocks ? partials[b * 2 + k] : 0.0;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) s[k] = block_sum256(v[k], red);
+    for (int k = 0; k < 4; ++k) w[k] = b < n_blocks ? ep_partials[b * 4 + k] : 0.0f;
+    double s[2];
+    float t[4];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) s[k] = block_sum256(v[k], red_d);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = block_sum256(w[k], red);
     if (b == 0) {
         moments[0] = s[0]; moments[1] = s[1]; moments[2] = count;
-        if (ep_totals) { ep_totals[0] += s[2]; ep_totals[1] += s[3]; ep_totals[2] += s[4]; ep_totals[3] += s[5]; }
+        if (ep_totals) { ep_totals[0] += t[0]; ep_totals[1] += t[1]; ep_totals[2] += t[2]; ep_totals[3] += t[3]; }
     }
 }
-__global__ __launch_bounds__(256) void returns_normalise_kernel(const float* __restrict__ adv, const float* __restrict__ moments, int M,
-                                                                 float* __restrict__ out) {
-    const float mean = moments[0] / moments[2];
-    const float var = fmaxf(moments[1] / moments[2] - mean * mean, 0.0f);
-    const float den = sqrtf(var) + 1e-6f;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) out[i] = (adv[i] - mean) / den;
+// Every WAVE pays the float64 prologue (two divisions, a square root, a reciprocal: ~150 VALU instructions) whatever its lanes do afterwards,
+// so the grid stops at 1024 blocks and a thread takes four elements per trip, a grid stride apart (four loads in flight): a quarter of the
+// prologues of an element per thread at 1 M elements.  The stride keeps block b on the 256-element chunks c = b (mod gridDim), which are
+// the chunks block b (mod 256) of the moments launch has just read — with blocks dealt round-robin over the 8 XCDs, the same XCD's L2.
+// (Four ADJACENT elements per thread, one 16-byte load, lose that: +1.3 us on the three launches at 16 x 65 536.)
+// out may alias adv: every element is read and written by the same thread, read first.
+constexpr int RET_NORM_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void returns_normalise_kernel(const float* adv, const double* __restrict__ moments, int M, float* out) {
+    const double mean = moments[0] / moments[2];
+    const double var = fmax(moments[1] / moments[2] - mean * mean, 0.0);
+    const double inv = 1.0 / (sqrt(var) + 1e-6);        // (a double reciprocal and product: 2^-52 of the quotient, nothing next to the store's 2^-24)
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += 4 * stride) {
+        float a[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[k] = i + k * stride < M ? adv[i + k * stride] : 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + k * stride < M) out[i + k * stride] = (float)(((double)a[k] - mean) * inv);
+    }
 }
 
 extern "C" int scg_ppo_returns_prepare(const uint8_t* d_done, const uint8_t* d_flags, const float* d_rew, const float* d_v_all, int T, int N,
@@ -1075,24 +1105,29 @@ extern "C" int scg_ppo_returns_prepare(const uint8_t* d_done, const uint8_t* d_f
     HIP_TRY(hipGetLastError());
     return 0;
 }
-extern "C" size_t scg_ppo_returns_scratch_bytes(void) { return (size_t)RET_BLOCKS * 8 * sizeof(float); }
-extern "C" int scg_ppo_returns_moments(const float* d_adv, int T, int N, float* d_episode_acc, float* d_scratch, float* d_moments,
+extern "C" size_t scg_ppo_returns_scratch_bytes(void) { return (size_t)RET_BLOCKS * (2 * sizeof(double) + 4 * sizeof(float)); }
+extern "C" int scg_ppo_returns_moments(const float* d_adv, int T, int N, float* d_episode_acc, void* d_scratch, double* d_moments,
                                        float* d_episode_totals, void* stream) {
     if (!d_adv || !d_scratch || !d_moments || T <= 0 || N <= 0) return fail(-1, "scg_ppo_returns_moments: bad argument");
+    if (((uintptr_t)d_scratch | (uintptr_t)d_moments) & 7) return fail(-1, "scg_ppo_returns_moments: d_scratch and d_moments hold doubles (8-byte alignment)");
     const long long M = (long long)T * N;
     if (M > 0x7fffffffLL) return fail(-1, "scg_ppo_returns_moments: T x N too large");
     const int grid = (int)std::min<long long>((M + 255) / 256, RET_BLOCKS);
-    returns_moments_kernel<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(d_adv, (int)M, d_episode_acc, N, d_scratch);
+    double* const partials = static_cast<double*>(d_scratch);
+    float* const ep_partials = reinterpret_cast<float*>(partials + RET_BLOCKS * 2);
+    returns_moments_kernel<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(d_adv, (int)M, d_episode_acc, N, partials, ep_partials);
     static_assert(RET_BLOCKS <= 256, "one partial row per thread of the finishing block");
-    returns_finish_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(d_scratch, grid, (float)M, d_moments, d_episode_acc ? d_episode_totals : nullptr);
+    returns_finish_kernel<<<dim3(1), dim3(256), 0, (hipStream_t)stream>>>(partials, ep_partials, grid, (double)M, d_moments,
+                                                                          d_episode_acc ? d_episode_totals : nullptr);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-extern "C" int scg_ppo_returns_normalise(const float* d_adv, const float* d_moments, int T, int N, float* d_out, void* stream) {
+extern "C" int scg_ppo_returns_normalise(const float* d_adv, const double* d_moments, int T, int N, float* d_out, void* stream) {
     if (!d_adv || !d_moments || !d_out || T <= 0 || N <= 0) return fail(-1, "scg_ppo_returns_normalise: bad argument");
+    if ((uintptr_t)d_moments & 7) return fail(-1, "scg_ppo_returns_normalise: d_moments holds doubles (8-byte alignment)");
     const long long M = (long long)T * N;
     if (M > 0x7fffffffLL) return fail(-1, "scg_ppo_returns_normalise: T x N too large");
-    const int grid = (int)std::min<long long>((M + 255) / 256, 4096);
+    const int grid = (int)std::min<long long>((M + 255) / 256, RET_NORM_BLOCKS);
     returns_normalise_kernel<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(d_adv, d_moments, (int)M, d_out);
     HIP_TRY(hipGetLastError());
     return 0;

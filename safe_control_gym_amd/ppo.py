@@ -165,6 +165,24 @@ def value_loss_term(ac, batch, clip_param, use_clipped_value):
     return 0.5 * (v_cur - ret).pow(2).mean()
 
 
+# ------------------------------------------------------------------ advantage normalisation (ppo.py:300)
+def advantage_moments(adv):
+    """float64 [3] = {sum adv, sum adv^2, count}, accumulated in float64: what one rank contributes to the global normalisation.  Ranks
+    combine by a plain SUM all-reduce of this vector.  (In float32 the variance sum adv^2 / n - mean^2 formed from these cancels as soon
+    as |mean| is large against std; float64 keeps ~8 digits of it at |mean| / std = 1e4 — normalization.RunningMeanStd's reason too.)"""
+    a = adv.detach().to(torch.float64)
+    return torch.stack([a.sum(), (a * a).sum(), torch.full((), float(a.numel()), dtype=torch.float64, device=a.device)])
+
+
+def normalise_advantages(adv, moments):
+    """(adv - mean) / (std + 1e-6), population std, from the (summed) float64 moments of advantage_moments or
+    scg_ppo_returns_moments; the arithmetic runs in float64 and rounds once, to adv's type."""
+    m = moments.to(torch.float64)
+    mean = m[0] / m[2]
+    std = torch.sqrt(torch.clamp(m[1] / m[2] - mean * mean, min=0.0))
+    return ((adv.to(torch.float64) - mean) / (std + 1e-6)).to(adv.dtype)
+
+
 class PPOAgent:
     def __init__(self, obs_dim, act_dim, cfg: PPOConfig, device):
         self.cfg = cfg
@@ -667,8 +685,8 @@ class PPO:
             self._mask = torch.zeros(T, N, **f)
             self._rew_c = torch.zeros(T, N, **f)
             self._adv_n = torch.zeros(T, N, **f)
-            self._moments = torch.zeros(3, **f)
-            self._ret_scratch = torch.zeros(int(D.scg_ppo_returns_scratch_bytes()) // 4, **f)
+            self._moments = torch.zeros(3, dtype=torch.float64, device=self.device)      # {sum adv, sum adv^2, count}: float64 on every path
+            self._ret_scratch = torch.zeros(int(D.scg_ppo_returns_scratch_bytes()) // 8, dtype=torch.float64, device=self.device)
         self.obs[0].copy_(self.obs_normalizer(env.reset_tensors()))
         # finished-episode statistics (VecRecordEpisodeStatistics), accumulated on device (four adjacent words: views of one vector)
         self._ep_tot = torch.zeros(4, device=self.device)
@@ -719,8 +737,7 @@ class PPO:
                 terminal_v[idx[:, 0], idx[:, 1]] = critic(self.term_obs[idx[:, 0], idx[:, 1]]).squeeze(-1)
         rew = rew_buf.clone()
         ret, adv = self._gae(rew, v_buf, mask, terminal_v, last_val, cfg.gamma, cfg.gae_lambda, cfg.use_gae)
-        moments = torch.stack([adv.sum(), (adv * adv).sum(), torch.full((), float(adv.numel()), device=adv.device)])
-        return ret, adv, moments
+        return ret, adv, advantage_moments(adv)
 
     # ---- fused rollout front end -----------------------------------------------------------------------------
     def _policy_struct(self, deterministic=False):
@@ -802,9 +819,7 @@ class PPO:
                                                                 C.c_void_p(self._adv_n.data_ptr()),
                                                                 C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
                 return self._adv_n
-            mean = moments[0] / moments[2]
-            std = torch.sqrt(torch.clamp(moments[1] / moments[2] - mean * mean, min=0.0))
-            return (adv - mean) / (std + 1e-6)
+            return normalise_advantages(adv, moments)
 
     def _rollout_data(self, ret, adv):
         M = self.T * self.N

@@ -29,14 +29,12 @@ import numpy as np
 import torch
 
 from safe_control_gym_amd import parallel
-from safe_control_gym_amd.ppo import PPO, PPOAgent, PPOConfig
+from safe_control_gym_amd.ppo import PPO, PPOAgent, PPOConfig, advantage_moments, normalise_advantages
 
 
 def _normalised(adv, moments):
     parallel.all_reduce_sum_(moments)
-    mean = moments[0] / moments[2]
-    std = torch.sqrt(torch.clamp(moments[1] / moments[2] - mean * mean, min=0.0))
-    return (adv - mean) / (std + 1e-6)
+    return normalise_advantages(adv, moments)
 
 
 class _TwoSided(PPO):
@@ -155,8 +153,7 @@ class _TwoSided(PPO):
         terminal_v = torch.where(trunc, tv, torch.zeros_like(tv))
         ret, adv = self._gae(rew_buf.clone(), v_all[:T].contiguous(), mask, terminal_v, v_all[T].contiguous(), cfg.gamma, cfg.gae_lambda,
                              cfg.use_gae)
-        moments = torch.stack([adv.sum(), (adv * adv).sum(), torch.full((), float(adv.numel()), device=adv.device)])
-        return ret, adv, moments
+        return ret, adv, advantage_moments(adv)
 
     @torch.no_grad()
     def _collect_fused_both(self):

@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from safe_control_gym_amd import parallel
-from safe_control_gym_amd.ppo import MLP, PPO, PPOConfig
+from safe_control_gym_amd.ppo import MLP, PPO, PPOConfig, normalise_advantages
 
 
 class SafetyLayer:
@@ -356,9 +356,7 @@ class SafeExplorerPPO(PPO):
         ret, adv, moments = self._returns_body(dense=False)
         with torch.no_grad():
             parallel.all_reduce_sum_(moments)
-            mean = moments[0] / moments[2]
-            std = torch.sqrt(torch.clamp(moments[1] / moments[2] - mean * mean, min=0.0))
-            adv = (adv - mean) / (std + 1e-6)
+            adv = normalise_advantages(adv, moments)
         M = self.T * self.N
         data = {'obs': self.obs[:self.T].reshape(M, self.obs_dim), 'act': self.act.reshape(M, self.act_dim),
                 'logp': self.logp.reshape(M), 'adv': adv.reshape(M), 'ret': ret.reshape(M), 'v': self.v.reshape(M),

@@ -210,7 +210,7 @@ def test_results_do_not_depend_on_the_launch_geometry(geometry, monkeypatch):
         monkeypatch.setenv('SCG_ROLLOUT_WPW', geo[1])
         env = _env(n, seed=3)
         sf = _filter().attach(env)
-        _, _, actor = _policy(env.device, False, scale=30.0, logstd=-0.5)
+        flat, _, actor = _policy(env.device, False, scale=30.0, logstd=-0.5)     # (flat held: actor points into its memory)
         outs.append(_rollout_cbf(env, sf, actor, k, False))
         env.close()
     for key in ('obs', 'act', 'logp', 'rew', 'done', 'flags', 'rows', 'applied', 'acc'):

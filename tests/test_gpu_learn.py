@@ -106,8 +106,8 @@ def test_one_tile_form_equals_the_accumulating_form(shape):
 
 def test_returns_post_processing_launches_equal_the_torch_ops():
     """scg_ppo_returns_prepare / _moments / _normalise (the collector's work between rollout and update, ppo.py:276-300) against the
-    PyTorch expressions they replace: flags and copies exactly, sums to float32 accumulation-order noise, the episode accumulators added to
-    the running totals and zeroed."""
+    PyTorch expressions they replace: flags and copies exactly, the (float64) moments to float64 accumulation-order noise, the episode
+    accumulators added to the running totals and zeroed.  (tests/test_gpu_returns.py: ill-conditioned inputs, every launch geometry.)"""
     from safe_control_gym_amd import _learn
     D = _learn.lib(12, 128, 2, 'tanh')
     T, N = 7, 1000
@@ -124,12 +124,14 @@ def test_returns_post_processing_launches_equal_the_torch_ops():
     adv = torch.randn(T, N, device='cuda', generator=g) * 3 + 0.5
     acc = torch.rand(N, 8, device='cuda', generator=g)
     acc0, totals = acc.clone(), torch.tensor([1.0, 2.0, 3.0, 4.0], device='cuda')
-    scratch = torch.zeros(int(D.scg_ppo_returns_scratch_bytes()) // 4, device='cuda')
-    mom, out = torch.zeros(3, device='cuda'), torch.empty(T, N, device='cuda')
+    scratch = torch.zeros(int(D.scg_ppo_returns_scratch_bytes()) // 8, dtype=torch.float64, device='cuda')
+    mom, out = torch.zeros(3, dtype=torch.float64, device='cuda'), torch.empty(T, N, device='cuda')       # the moments are doubles
     _learn.check(D, D.scg_ppo_returns_moments(p(adv), T, N, p(acc), p(scratch), p(mom), p(totals), st))
     _learn.check(D, D.scg_ppo_returns_normalise(p(adv), p(mom), T, N, p(out), st))
     torch.cuda.synchronize()
-    torch.testing.assert_close(mom, torch.stack([adv.sum(), (adv * adv).sum(), torch.tensor(float(T * N), device='cuda')]), rtol=1e-5, atol=1e-3)
+    a64 = adv.double()              # float64 accumulation: 7000 terms of ~1e1 leave ~1e-11 of summation-order noise
+    torch.testing.assert_close(mom, torch.stack([a64.sum(), (a64 * a64).sum(), torch.tensor(float(T * N), dtype=torch.float64, device='cuda')]),
+                               rtol=1e-12, atol=1e-9)
     torch.testing.assert_close(totals, torch.tensor([1.0, 2.0, 3.0, 4.0], device='cuda') + acc0.sum(0)[:4], rtol=1e-5, atol=1e-4)
     assert (acc == 0).all()
     torch.testing.assert_close(out, (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-6), rtol=1e-4, atol=1e-5)

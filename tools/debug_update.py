@@ -2,7 +2,7 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from safe_control_gym_amd.ppo import PPO, PPOConfig, PPOAgent
+from safe_control_gym_amd.ppo import PPO, PPOConfig, PPOAgent, normalise_advantages
 from safe_control_gym_amd.registration import load_task
 from safe_control_gym_amd.vec_env import HipVecEnv
 torch.cuda.set_device(0)
@@ -17,8 +17,7 @@ for _ in range(int(sys.argv[1]) if len(sys.argv) > 1 else 1):
 # iteration-2 data
 ppo._rollout_graph.replay()
 ret, adv, moments = ppo._rollout_out
-mean = moments[0] / moments[2]; std = torch.sqrt(torch.clamp(moments[1] / moments[2] - mean * mean, min=0.0))
-adv = (adv - mean) / (std + 1e-6)
+adv = normalise_advantages(adv, moments)
 M = T * N
 data = {'obs': ppo.obs[:T].reshape(M, -1).clone(), 'act': ppo.act.reshape(M, -1).clone(), 'logp': ppo.logp.reshape(M).clone(),
         'adv': adv.reshape(M).clone(), 'ret': ret.reshape(M).clone(), 'v': ppo.v.reshape(M).clone()}
