@@ -12,8 +12,12 @@ from safe_control_gym_amd import _lib as L
 
 SRC = os.path.join(L.CSRC_DIR, 'scg_safe_explorer.hip')
 HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_safe_explorer.h'))
-# the env library's hash inputs (_lib.SOURCES + _lib.HEADERS), the adversarial header the ABI includes, and the two new files
-DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, SRC, HEADER]
+# the pre-training kernels (collector + fused constraint-model update) ride in the same library: csrc/scg_safe_pretrain.h + its ABI
+PRETRAIN_SRC = os.path.join(L.CSRC_DIR, 'scg_safe_pretrain.h')
+PRETRAIN_HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_safe_pretrain.h'))
+# the env library's hash inputs (_lib.SOURCES + _lib.HEADERS), the adversarial header the ABI includes, and this library's own files
+DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, SRC, HEADER, PRETRAIN_SRC, PRETRAIN_HEADER,
+                                                                       os.path.join(L.CSRC_DIR, 'scg_adam.h')]
 PREFIX = 'libscg_saferoll_'
 LDS_BUDGET = 163840                 # 160 KiB of LDS per CU (MI355X)
 MAX_CONSTRAINTS, MAX_HIDDEN_C = 32, 256
@@ -66,6 +70,47 @@ def supported(obs_dim, hidden, act_dim, activation, n_constraints, hidden_c):
         hidden_c = hidden_c[0]
     return (L.policy_supported(obs_dim, hidden, act_dim, activation) and 1 <= int(n_constraints) <= MAX_CONSTRAINTS
             and 1 <= int(hidden_c) <= MAX_HIDDEN_C and placement(obs_dim, hidden, act_dim, n_constraints, hidden_c) is not None)
+
+
+def flat_words(obs_dim, act_dim, hidden_c):
+    """P: the float words of ONE constraint model in scg_safety_update's flat layout  W1 [Hc][obs] | b1 [Hc] | W2 [A][Hc] | b2 [A]."""
+    return int(hidden_c) * (int(obs_dim) + 1 + int(act_dim)) + int(act_dim)
+
+
+def pretrain_lds_bytes(obs_dim, act_dim, hidden_c):
+    """LDS bytes per workgroup of scg_safety_update (csrc/scg_safe_pretrain.h, PretrainShape): parameters, both Adam moments and the
+    gradient of one constraint model, the waves' loss partials, and a chunk of 1024 staged rows (halved while over budget, down to 32)."""
+    fixed = 4 * ((flat_words(obs_dim, act_dim, hidden_c) + 3) // 4 * 4) + 16
+    roww = int(obs_dim) + int(act_dim) + 1
+    rc = 1024
+    while rc >= 64 and (fixed + rc * roww) * 4 > LDS_BUDGET:
+        rc //= 2
+    return (fixed + rc * roww) * 4
+
+
+def supported_pretrain(obs_dim, act_dim, n_constraints, hidden_c):
+    """Shapes scg_collect_constraints / scg_safety_update serve: 1..32 constraints, one hidden layer of 1..256, at most 32 inputs and 4
+    actions, and an LDS need within 160 KiB.  (The library itself is compiled per actor shape too: _safe_explorer.supported.)"""
+    if isinstance(hidden_c, (list, tuple)):
+        if len(hidden_c) != 1:
+            return False
+        hidden_c = hidden_c[0]
+    return (isinstance(hidden_c, int) and 1 <= int(n_constraints) <= MAX_CONSTRAINTS and 1 <= hidden_c <= MAX_HIDDEN_C
+            and 1 <= int(act_dim) <= 4 and 1 <= int(obs_dim) <= 32 and pretrain_lds_bytes(obs_dim, act_dim, hidden_c) <= LDS_BUDGET)
+
+
+class CollectIO(C.Structure):
+    """scg_collect_io (include/scg_safe_pretrain.h)."""
+    _fields_ = [('d_obs', C.c_void_p), ('d_act', C.c_void_p), ('d_c', C.c_void_p), ('d_c_next', C.c_void_p), ('pos', C.c_int64),
+                ('capacity', C.c_int64), ('low', C.c_float * 4), ('high', C.c_float * 4), ('d_c_carry', C.c_void_p),
+                ('d_last_obs', C.c_void_p), ('d_ep_stats', C.c_void_p)]
+
+
+class SafetyUpdateArgs(C.Structure):
+    """scg_safety_update_args (include/scg_safe_pretrain.h)."""
+    _fields_ = [('d_params', C.c_void_p), ('d_m', C.c_void_p), ('d_v', C.c_void_p), ('d_steps', C.c_void_p), ('d_obs', C.c_void_p),
+                ('d_act', C.c_void_p), ('d_c', C.c_void_p), ('d_c_next', C.c_void_p), ('d_rows', C.c_void_p), ('n_batches', C.c_int32),
+                ('batch', C.c_int32), ('lr', C.c_float), ('train', C.c_int32), ('d_loss', C.c_void_p), ('d_grad', C.c_void_p)]
 
 
 def pack_safety_layer(models, obs_dim, act_dim, hidden_c, out=None):
@@ -142,7 +187,7 @@ _libs = {}
 
 
 def lib_for(cfg, hidden, activation, hidden_c):
-    """The bound library (every _lib.EXPORTS symbol + scg_rollout_safe), built now if missing or stale."""
+    """The bound library (every _lib.EXPORTS symbol + scg_rollout_safe + the pre-training entry points), built now if missing or stale."""
     _, h = L.spec_source(cfg)
     key = (h, int(hidden), activation, int(hidden_c))
     if key in _libs:
@@ -159,6 +204,9 @@ def lib_for(cfg, hidden, activation, hidden_c):
                                    C.POINTER(L.PolicyRollout), C.c_void_p, C.c_void_p, C.c_void_p]
     D.scg_safe_explorer_shape.argtypes = [C.POINTER(C.c_int32)] * 7
     D.scg_safe_explorer_lds.argtypes = [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    D.scg_collect_constraints.argtypes = [C.c_void_p, C.c_int, C.POINTER(CollectIO), C.c_void_p]
+    D.scg_safety_update.argtypes = [C.POINTER(SafetyUpdateArgs), C.c_void_p]
+    D.scg_safe_pretrain_lds.argtypes = [C.POINTER(C.c_int32)]
     shape = [C.c_int32() for _ in range(7)]
     D.scg_safe_explorer_shape(*[C.byref(v) for v in shape])
     if tuple(v.value for v in shape[1:4]) != (int(hidden_c), int(hidden), L.POLICY_ACTS[activation]):
@@ -172,6 +220,13 @@ def shape_of(D):
     v = [C.c_int32() for _ in range(7)]
     D.scg_safe_explorer_shape(*[C.byref(x) for x in v])
     return tuple(x.value for x in v)
+
+
+def pretrain_lds_of(D):
+    """LDS bytes per workgroup scg_safety_update uses in this bound library."""
+    b = C.c_int32()
+    L.check(D.scg_safe_pretrain_lds(C.byref(b)), D)
+    return b.value
 
 
 def launch_plan(D, wpw):

@@ -375,15 +375,20 @@ class SafeExplorerPPO(PPO):
     Extension key `fused_rollout=True` (not in SAFE_EXPLORER_PPO_DEFAULTS, which equal the YAML): the training and evaluation envs are
     built with the actor's and the safety layer's shape (HipVecEnv(..., policy=(hidden_dim, activation), safety_layer=
     constraint_hidden_dim)), so that the PPO phase collects with one scg_rollout_safe launch and run() evaluates with one.  An
-    unservable shape, a safety layer of more than one hidden layer or a running normaliser warns and keeps the eager path; the
-    pre-training phase always runs eagerly (random actions, not the policy)."""
+    unservable shape, a safety layer of more than one hidden layer or a running normaliser warns and keeps the eager path.
+    Extension key `fused_pretrain=True` (not a default either, independent of `fused_rollout`): the envs are built on the same library and
+    the pre-training phase runs fused — an epoch is one scg_collect_constraints launch (random actions drawn in the kernel, transitions
+    written to the constraint buffer's ring) and one scg_safety_update launch for all its minibatches; eval_constraint_models takes the
+    same two launches in loss-only mode.  Checkpoints keep upstream's keys: a fused run resumes eagerly and the other way round.  Without
+    the key the pre-training phase runs eagerly, step by step."""
     DEFAULTS = SAFE_EXPLORER_PPO_DEFAULTS
 
     def _safety_shape(self):
-        """(policy, safety_layer) arguments of the envs: the fused collector's shape when asked for and servable, else (None, None)."""
+        """(policy, safety_layer) arguments of the envs: the fused collector's shape when `fused_rollout` or `fused_pretrain` asks for the
+        saferoll library and it serves the shape, else (None, None)."""
         from safe_control_gym_amd import _safe_explorer
         from safe_control_gym_amd.env_config import EnvSpec
-        if not self.algo_config.get('fused_rollout') or self.norm_obs or self.norm_reward:
+        if not (self.algo_config.get('fused_rollout') or self.algo_config.get('fused_pretrain')) or self.norm_obs or self.norm_reward:
             return None, None
         hc = self.constraint_hidden_dim
         if isinstance(hc, (list, tuple)):

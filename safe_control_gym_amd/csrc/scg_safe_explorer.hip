@@ -452,3 +452,6 @@ extern "C" int scg_rollout_safe(scg_env* env, const scg_actor_ptrs* actor, const
     return fail(SCG_ERR_INVALID, "scg_rollout_safe serves float32 envs");
 #endif
 }
+
+// Safe-Explorer pre-training: the random-action transition collector and the fused constraint-model update (include/scg_safe_pretrain.h)
+#include "scg_safe_pretrain.h"

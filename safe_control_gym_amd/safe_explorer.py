@@ -38,6 +38,113 @@ class SafetyLayer:
             slack = [slack] * self.num_constraints
         self.slack = torch.as_tensor(slack, dtype=torch.float32, device=self.device)
         self.optimizers = [torch.optim.Adam(m.parameters(), lr=lr) for m in self.constraint_models]
+        self._flat = None                        # flat storage of the fused update (flatten()); None: the plain eager layer
+
+    # ---- flat storage + the fused update (include/scg_safe_pretrain.h): opt-in, the eager methods keep working on the same parameters
+    def flatten(self, lib=None):
+        """Move the parameters into ONE [C][P] float32 buffer (per constraint: W1 | b1 | W2 | b2, the optimisers' parameter order) with the
+        nn.Parameters as views into it, next to flat Adam moments and step counts: what scg_safety_update reads and writes.  `lib` is the
+        bound saferoll library of this shape (update_fused needs it).  One hidden layer only."""
+        models = self.constraint_models
+        if any(len(m.fcs) != 2 for m in models):
+            raise ValueError('flat storage serves safety layers with one hidden layer')
+        if self._flat is None:
+            P = sum(p.numel() for p in models[0].parameters())
+            f = dict(dtype=torch.float32, device=self.device)
+            buf = torch.zeros(self.num_constraints, P, **f)
+            with torch.no_grad():
+                for i, m in enumerate(models):
+                    o = 0
+                    for p in m.parameters():                     # fcs.0.weight, fcs.0.bias, fcs.1.weight, fcs.1.bias
+                        k = p.numel()
+                        buf[i, o:o + k].copy_(p.detach().reshape(-1))
+                        p.data = buf[i, o:o + k].view(p.shape)
+                        o += k
+            self._flat = {'p': buf, 'm': torch.zeros_like(buf), 'v': torch.zeros_like(buf), 'steps': torch.zeros(self.num_constraints, **f),
+                          'lib': None, 'moments': 'opt'}         # 'moments': which side holds the current Adam state
+        if lib is not None:
+            self._flat['lib'] = lib
+        return self
+
+    def _offsets(self, i):
+        o = 0
+        for p in self.constraint_models[i].parameters():
+            yield p, o, p.numel()
+            o += p.numel()
+
+    def _moments_to_optimizers(self):
+        """torch.optim's `state` filled from the flat moments (upstream's checkpoint keys; an optimiser that never stepped stays empty)."""
+        fl = self._flat
+        steps = fl['steps'].tolist()
+        for i, opt in enumerate(self.optimizers):
+            if steps[i] <= 0:
+                opt.state.clear()
+                continue
+            for p, o, k in self._offsets(i):
+                opt.state[p] = {'step': torch.tensor(float(steps[i])), 'exp_avg': fl['m'][i, o:o + k].view(p.shape).clone(),
+                                'exp_avg_sq': fl['v'][i, o:o + k].view(p.shape).clone()}
+
+    def _moments_from_optimizers(self):
+        fl = self._flat
+        for i, opt in enumerate(self.optimizers):
+            n_steps = 0.0
+            for p, o, k in self._offsets(i):
+                st = opt.state.get(p)
+                if not st:
+                    fl['m'][i, o:o + k].zero_()
+                    fl['v'][i, o:o + k].zero_()
+                    continue
+                fl['m'][i, o:o + k].copy_(st['exp_avg'].reshape(-1))
+                fl['v'][i, o:o + k].copy_(st['exp_avg_sq'].reshape(-1))
+                n_steps = float(st['step'])
+            fl['steps'][i] = n_steps
+
+    def update_fused(self, buffer, rows, batch, train=True, grad=None, check_rows=True):
+        """rows.numel() // batch minibatches of update() (train) or compute_loss() (not train) in ONE scg_safety_update launch: `buffer` a
+        ConstraintBuffer (or its dict of ring tensors), `rows` an int32 device tensor of ring rows, minibatch k = rows[k * batch:(k + 1) *
+        batch].  Every entry must be a valid ring row: the kernel does not check, so this method does (one read-back) unless the caller
+        vouches for them with check_rows=False (a permutation of the filled rows).  Returns the losses [n_batches, C], each under the
+        parameters before that minibatch's step.  grad: an optional [C, P] float32 tensor for the last minibatch's gradient."""
+        import ctypes as C
+        from safe_control_gym_amd import _lib as L
+        from safe_control_gym_amd import _safe_explorer
+        fl = self._flat
+        if fl is None or fl['lib'] is None:
+            raise L.ScgError('SafetyLayer.update_fused needs flatten(lib) with the bound saferoll library of this shape')
+        data = buffer.data if hasattr(buffer, 'data') else buffer
+        batch = int(batch)
+        if rows.dtype != torch.int32 or not rows.is_contiguous() or rows.device != fl['p'].device or batch < 1 or rows.numel() < batch:
+            raise ValueError('rows must be a contiguous int32 tensor on the layer device holding at least one minibatch')
+        n_batches = rows.numel() // batch
+        if check_rows and not (0 <= int(rows.min()) and int(rows.max()) < data['obs'].shape[0]):
+            raise ValueError(f'rows must lie in [0, {data["obs"].shape[0]})')
+        if not (data['act'].shape[0] == data['c'].shape[0] == data['c_next'].shape[0] == data['obs'].shape[0]):
+            raise ValueError('the ring arrays must have the same number of rows')
+        obs_dim, act_dim = data['obs'].shape[1], data['act'].shape[1]
+        shape = _safe_explorer.shape_of(fl['lib'])
+        hc = self.constraint_models[0].fcs[0].out_features
+        if (shape[0], shape[1], shape[4], shape[5]) != (self.num_constraints, hc, act_dim, obs_dim) or \
+                fl['p'].shape[1] != _safe_explorer.flat_words(obs_dim, act_dim, hc) or data['c'].shape[1] != self.num_constraints:
+            raise ValueError('the bound library was built for another (C, Hc, act_dim, obs_dim)')
+        for t in (data['obs'], data['act'], data['c'], data['c_next']) + ((grad,) if grad is not None else ()):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != fl['p'].device:
+                raise ValueError('the ring arrays (and grad) must be contiguous float32 tensors on the layer device')
+        if grad is not None and grad.shape != fl['p'].shape:
+            raise ValueError(f'grad must be {tuple(fl["p"].shape)}')
+        if train and fl['moments'] == 'opt':
+            self._moments_from_optimizers()
+        loss = torch.empty(n_batches, self.num_constraints, dtype=torch.float32, device=fl['p'].device)
+        a = _safe_explorer.SafetyUpdateArgs()
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        a.d_params, a.d_m, a.d_v, a.d_steps = p(fl['p']), p(fl['m']), p(fl['v']), p(fl['steps'])
+        a.d_obs, a.d_act, a.d_c, a.d_c_next, a.d_rows = p(data['obs']), p(data['act']), p(data['c']), p(data['c_next']), p(rows)
+        a.n_batches, a.batch, a.lr, a.train = n_batches, batch, float(self.optimizers[0].param_groups[0]['lr']), int(bool(train))
+        a.d_loss, a.d_grad = p(loss), (p(grad) if grad is not None else None)
+        with torch.cuda.device(fl['p'].device):
+            L.check(fl['lib'].scg_safety_update(C.byref(a), C.c_void_p(torch.cuda.current_stream(fl['p'].device).cuda_stream)), fl['lib'])
+        if train:
+            fl['moments'] = 'flat'
+        return loss
 
     def g(self, obs):
         """[B, C, A]: the learned sensitivities of every constraint to the action."""
@@ -49,6 +156,9 @@ class SafetyLayer:
         return ((batch['c_next'] - pred) ** 2).mean(0)                    # [C]
 
     def update(self, batch):
+        if self._flat is not None and self._flat['moments'] == 'flat':      # fused steps came first: the optimisers continue from them
+            self._moments_to_optimizers()
+            self._flat['moments'] = 'opt'
         losses = self.compute_loss(batch)
         for opt in self.optimizers:
             opt.zero_grad()
@@ -68,12 +178,21 @@ class SafetyLayer:
         return act - max_mult[:, None] * max_g
 
     def state_dict(self):
+        """Upstream's keys either way: with flat storage the fused Adam moments travel in torch.optim's layout (ddpg.DDPGAgent's precedent),
+        so that a fused run resumes eagerly and an eager run resumes fused."""
+        if self._flat is not None and self._flat['moments'] == 'flat':
+            self._moments_to_optimizers()
         return {'constraint_models': self.constraint_models.state_dict(), 'optimizers': [o.state_dict() for o in self.optimizers]}
 
     def load_state_dict(self, sd):
-        self.constraint_models.load_state_dict(sd['constraint_models'])
-        for o, s in zip(self.optimizers, sd['optimizers']):
+        self.constraint_models.load_state_dict(sd['constraint_models'])      # (in place: the flat buffer, when there is one, follows)
+        for o, s in zip(self.optimizers, sd.get('optimizers', [])):
             o.load_state_dict(s)
+            for st in o.state.values():
+                if torch.is_tensor(st.get('step')):
+                    st['step'] = st['step'].cpu()
+        if self._flat is not None and sd.get('optimizers'):
+            self._flat['moments'] = 'opt'                                    # read back into the flat moments by the next fused update
 
 
 class ConstraintBuffer:
@@ -122,6 +241,60 @@ class SafeExplorerPPO(PPO):
         self.obs[0].copy_(self.obs_normalizer(env.reset_tensors()))
         self.c = self._reset_c(env.out)
         self._setup_fused(constraint_hidden_dim)
+        self._setup_fused_pretrain(constraint_hidden_dim)
+
+    def _setup_fused_pretrain(self, hidden_c):
+        """The fused pre-training phase when cfg.extra['fused_pretrain'] is set: one scg_collect_constraints launch per
+        collection, one scg_safety_update launch for all minibatches of an epoch.  Needs an env on the saferoll library of this shape, a
+        servable safety layer, no running normaliser and a ring that holds at least one step of every env; otherwise (when asked for) one
+        warning and the eager path."""
+        from safe_control_gym_amd import _safe_explorer
+        self._fused_pretrain = False
+        if not self.cfg.extra.get('fused_pretrain'):
+            return
+        hc = hidden_c[0] if isinstance(hidden_c, (list, tuple)) and len(hidden_c) == 1 else hidden_c
+        shape = getattr(self.env, 'safety_shape', None)
+        ok = (isinstance(hc, int) and shape is not None and shape[2] == hc and not self._normalise
+              and self.env.dtype == torch.float32 and self.constraint_buffer.capacity >= self.N
+              and _safe_explorer.supported_pretrain(self.obs_dim, self.act_dim, self.C, hc))
+        if not ok:
+            warnings.warn(f'SafeExplorerPPO: no fused pre-training for env shape {shape} / safety hidden width {hidden_c} (normalisers: '
+                          f'{bool(self._normalise)}, ring {self.constraint_buffer.capacity} rows for {self.N} envs); using the eager '
+                          'pre-training', RuntimeWarning, stacklevel=3)
+            return
+        self.safety_layer.flatten(self.env._lib)
+        self._fused_pretrain = True
+        self._pre_last_obs = torch.zeros(self.N, self.obs_dim, device=self.device)
+
+    def _collect_constraint_data_fused(self, num_steps):
+        """collect_constraint_data as ONE scg_collect_constraints launch (more only when the ring holds fewer rows than the request)."""
+        env, buf = self.env, self.constraint_buffer
+        env.reset_tensors()
+        self.c = self._reset_c(env.out)
+        carry = self._carry()
+        left = -(-int(num_steps) // (self.N * parallel.world_size()))
+        per = buf.capacity // self.N
+        while left > 0:
+            k = min(left, per)
+            env.collect_constraints(k, buf.data, buf.pos, carry, self._pre_last_obs)
+            buf.pos = (buf.pos + k * self.N) % buf.capacity
+            buf.size = min(buf.size + k * self.N, buf.capacity)
+            left -= k
+        self.obs[0].copy_(self._pre_last_obs)
+
+    def _fused_minibatches(self, batch_size, train):
+        """One pass of shuffled minibatches over the buffer (ConstraintBuffer.sampler's permutation, last partial minibatch dropped) as
+        ONE scg_safety_update launch.  Returns the mean per-constraint losses as a [C] tensor."""
+        buf = self.constraint_buffer
+        bs = min(int(batch_size), buf.size)
+        k = buf.size // bs if bs > 0 else 0
+        if k == 0:
+            return torch.zeros(self.C, device=self.device)
+        perm = torch.randperm(buf.size, device=self.device)
+        losses = self.safety_layer.update_fused(buf, perm[:k * bs].to(torch.int32).contiguous(), bs, train=train, check_rows=False)
+        if train:                                   # kernel writes do not bump the parameters' version counters
+            self._safety_packed = None
+        return losses.sum(0) / k
 
     def _setup_fused(self, hidden_c):
         """The fused collector when cfg.extra['fused_rollout'] is set, the env carries the matching (hidden, activation, Hc) shape and
@@ -188,6 +361,8 @@ class SafeExplorerPPO(PPO):
 
     # ---- pre-training of the constraint models (safe_ppo.py:196-296, :425-449)
     def collect_constraint_data(self, num_steps):
+        if self._fused_pretrain:
+            return self._collect_constraint_data_fused(num_steps)
         env = self.env
         low = torch.as_tensor(env.spec.action_space.low, dtype=torch.float32, device=self.device)
         high = torch.as_tensor(env.spec.action_space.high, dtype=torch.float32, device=self.device)
@@ -209,6 +384,10 @@ class SafeExplorerPPO(PPO):
         minibatches over them, buffer cleared.  Returns the mean per-constraint losses."""
         self.obs_normalizer.unset_read_only()
         self.collect_constraint_data(steps_per_epoch)
+        if self._fused_pretrain:
+            mean = self._fused_minibatches(batch_size or self.constraint_batch_size, train=True)
+            self.constraint_buffer.pos = self.constraint_buffer.size = 0
+            return mean.tolist()
         bs = min(int(batch_size or self.constraint_batch_size), self.constraint_buffer.size)
         acc, k = torch.zeros(self.C, device=self.device), 0
         for batch in self.constraint_buffer.sampler(bs):
@@ -224,6 +403,10 @@ class SafeExplorerPPO(PPO):
         self.obs_normalizer.set_read_only()
         self.collect_constraint_data(num_steps)
         self.obs_normalizer.read_only = frozen
+        if self._fused_pretrain:
+            mean = self._fused_minibatches(batch_size or self.constraint_batch_size, train=False)
+            self.constraint_buffer.pos = self.constraint_buffer.size = 0
+            return mean.tolist()
         bs = min(int(batch_size or self.constraint_batch_size), self.constraint_buffer.size)
         acc, k = torch.zeros(self.C, device=self.device), 0
         for batch in self.constraint_buffer.sampler(bs):
@@ -310,15 +493,15 @@ class SafeExplorerPPO(PPO):
             if os.path.isdir(p):
                 p = os.path.join(p, 'model_latest.pt')
             state_or_path = torch.load(p, map_location='cpu', weights_only=False)
-        sd = state_or_path['safety_layer']
-        self.safety_layer.constraint_models.load_state_dict(sd['constraint_models'])
-        for o, st in zip(self.safety_layer.optimizers, sd.get('optimizers', [])):
-            o.load_state_dict(st)
+        self.safety_layer.load_state_dict(state_or_path['safety_layer'])
 
     def pretrain(self, num_steps, epochs=5):
         self.collect_constraint_data(num_steps)
         hist = []
         for _ in range(epochs):
+            if self._fused_pretrain:
+                hist.append(self._fused_minibatches(self.constraint_batch_size, train=True).tolist())
+                continue
             acc, k = torch.zeros(self.C, device=self.device), 0
             for batch in self.constraint_buffer.sampler(min(self.constraint_batch_size, self.constraint_buffer.size)):
                 acc += self.safety_layer.update(batch)

@@ -529,6 +529,39 @@ class HipVecEnv(VecEnv):
             self._chk(self._lib.scg_rollout_safe(self._h, C.byref(actor), p(safety), p(slack), int(bool(deterministic)), int(k_steps),
                                                  C.byref(o), p(c_rows), p(c_carry), self._stream()))
 
+    def collect_constraints(self, k_steps, ring, pos, c_carry, last_obs):
+        """K control steps with in-kernel uniform random actions in ONE launch (scg_collect_constraints), every step's transition written
+        to the caller's ring: `ring` is a dict of float32 tensors obs [cap, obs_dim], act [cap, nu], c [cap, C], c_next [cap, C]; step t
+        of env i goes to row (pos + t * N + i) % cap.  c_carry [N, C] holds the constraint values of the current state (read, then
+        overwritten with those after the last step), last_obs [N, obs_dim] receives the observation after the last step.  Needs
+        k_steps * N <= cap (the library refuses otherwise: two envs would share a row)."""
+        if self.safety_shape is None:
+            raise L.ScgError('this env was not built with a safety-layer shape (HipVecEnv(..., policy=(hidden, activation), safety_layer=Hc))')
+        from safe_control_gym_amd import _safe_explorer
+        C_, nobs, nu = self.spec.n_state_con_rows, self.spec.obs_dim, self.spec.nu
+        cap = int(ring['obs'].shape[0])
+        want = {'obs': (cap, nobs), 'act': (cap, nu), 'c': (cap, C_), 'c_next': (cap, C_)}
+        for k, shp in want.items():
+            if tuple(ring[k].shape) != shp:
+                raise ValueError(f'ring[{k!r}] must be [{shp[0]}, {shp[1]}]')
+        if c_carry.shape != (self.num_envs, C_) or last_obs.shape != (self.num_envs, nobs):
+            raise ValueError(f'c_carry must be [{self.num_envs}, {C_}] and last_obs [{self.num_envs}, {nobs}]')
+        for t in (ring['obs'], ring['act'], ring['c'], ring['c_next'], c_carry, last_obs):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('the ring arrays, c_carry and last_obs must be contiguous float32 tensors on the env device')
+        if not 0 <= int(pos) < cap:
+            raise ValueError(f'pos must be a ring row (0 <= pos < {cap})')
+        io = _safe_explorer.CollectIO()
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        io.d_obs, io.d_act, io.d_c, io.d_c_next = p(ring['obs']), p(ring['act']), p(ring['c']), p(ring['c_next'])
+        io.pos, io.capacity = int(pos), cap
+        low, high = self.spec.action_space.low, self.spec.action_space.high
+        for j in range(nu):
+            io.low[j], io.high[j] = float(low[j]), float(high[j])
+        io.d_c_carry, io.d_last_obs, io.d_ep_stats = p(c_carry), p(last_obs), p(self.ep_stats)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_collect_constraints(self._h, int(k_steps), C.byref(io), self._stream()))
+
     def certify_tensors(self, params, states, actions, certified=None, slack=None, feasible=None):
         """The CBF-QP's minimiser for n (state, physical action) rows in ONE launch (scg_cbf_certify): `params` an _cbf.CbfParams
         (cbf.CBF.params()), `states` float32 [n, 4], `actions` float32 [n]; n is independent of the env count.  Returns (and fills, when
