@@ -4,7 +4,11 @@ stabilisation task of the reference's examples/lqr (ctrl_freq 15, pyb_freq 750, 
 cart position and the pole angle swept.  Each LQR evaluation and each iLQR iteration is one closed-loop launch (scg_rollout_feedback);
 the iLQR backward pass is one more (scg_ilqr_backward).  Prints the LQR cost and the iLQR cost per state.
 
-usage: run_ilqr.py [--points 8] [--iterations 15] [--dtype float64]"""
+--system quadrotor_3D runs the same comparison on the 12-state, 4-input Quadrotor 3D (the stabilisation task of
+tests/golden/ilqr3d_settings.json, the start position swept in x and y) with the extension key wide_backward=True: the LDS-resident
+backward pass (scg_ilqr_backward_wide, include/scg_ilqr_wide.h).
+
+usage: run_ilqr.py [--system cartpole|quadrotor_3D] [--points 8] [--iterations 15] [--dtype float64]"""
 import argparse
 import json
 import os
@@ -24,7 +28,10 @@ def main():
     ap.add_argument('--points', type=int, default=8, help='grid points per swept dimension')
     ap.add_argument('--iterations', type=int, default=15)
     ap.add_argument('--dtype', default='float64', choices=['float32', 'float64'])
+    ap.add_argument('--system', default='cartpole', choices=['cartpole', 'quadrotor_3D'])
     a = ap.parse_args()
+    if a.system == 'quadrotor_3D':
+        return quadrotor_3d(a)
     with open(os.path.join(ROOT, 'tests', 'golden', 'ilqr_settings.json')) as f:
         case = json.load(f)['cases']['cartpole_stab']
     env_func = partial(make, case['env'], **case['task'])
@@ -42,6 +49,32 @@ def main():
     for i, s in enumerate(x0):
         note = '  (LQR leaves the bounds: no iLQR update)' if unstable[i] else ''
         print(f'{s[0]:7.3f} {s[2]:7.3f} {lqr_cost[i]:12.5f} {ilqr_cost[i]:12.5f} {int(best_it[i]):8d} {lamb[i]:8.1f}{note}')
+    ilqr.close()
+
+
+def quadrotor_3d(a):
+    with open(os.path.join(ROOT, 'tests', 'golden', 'ilqr3d_settings.json')) as f:
+        case = json.load(f)['cases']['q3_stab']
+    env_func = partial(make, case['env'], **case['task'])
+    n = a.points * a.points
+    algo = dict(case['algo'], max_iterations=a.iterations)
+    lqr = make('lqr', env_func, num_envs=n, dtype=a.dtype, q_lqr=algo['q_lqr'], r_lqr=algo['r_lqr'])
+    lqr.reset()
+    # raw simulator states (include/scg_hip.h: pos[3], quat[4], vel[3], ang_vel[3]): the task's own start, x and y swept
+    x0 = np.array(lqr._x0, dtype=np.float64).reshape(n, -1)
+    grid = np.linspace(-0.6, 0.6, a.points)
+    x0[:, 0], x0[:, 1] = np.repeat(grid, a.points), np.tile(grid, a.points)
+    lqr.set_initial_states(x0)
+    lqr_cost = -lqr.run()['ep_returns']
+    lqr.close()
+    ilqr = make('ilqr', env_func, num_envs=n, dtype=a.dtype, init_states=x0, wide_backward=True, **algo)
+    ilqr.learn()
+    ilqr_cost = -ilqr.run()['ep_returns']
+    unstable, best_it, lamb = (np.atleast_1d(v) for v in (ilqr.initial_policy_unstable, ilqr.best_iteration, ilqr.lamb))
+    print(f'{"x":>7} {"y":>7} {"LQR cost":>12} {"iLQR cost":>12} {"best it":>8} {"lambda":>8}')
+    for i, s in enumerate(x0):
+        note = '  (LQR leaves the bounds: no iLQR update)' if unstable[i] else ''
+        print(f'{s[0]:7.3f} {s[1]:7.3f} {lqr_cost[i]:12.5f} {ilqr_cost[i]:12.5f} {int(best_it[i]):8d} {lamb[i]:8.1f}{note}')
     ilqr.close()
 
 

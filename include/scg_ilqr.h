@@ -57,7 +57,8 @@ int scg_rollout_feedback(scg_env* env, int k_steps, const scg_feedback_rollout* 
  *   d_x T [k_steps + 1][nx][N] (row n_steps[i] holds env i's final observation), d_u T [k_steps][nu][N], d_n_steps int32 [N] (1..k_steps),
  *   d_lamb T [N]; d_gains T [k_steps][nu][nx][N] and d_ff T [k_steps][nu][N] are updated in place; d_unstable uint8 [N] is SET to 1
  *   where H was not finite and otherwise left alone.
- * Serves CartPole, Quadrotor 1D and 2D; Quadrotor 3D returns SCG_ERR_INVALID (nu = 4 needs another eigen-solve and register budget). */
+ * Serves CartPole, Quadrotor 1D and 2D; Quadrotor 3D returns SCG_ERR_INVALID (nu = 4 needs another eigen-solve and register budget):
+ * scg_ilqr_backward_wide (scg_ilqr_wide.h) serves it. */
 typedef struct scg_ilqr_model {
     double q[12];               /* diagonal of Q (nx used) */
     double r[4];                /* diagonal of R (nu used) */

@@ -1,6 +1,7 @@
 """ctypes binding + builder of libscg_ilqr_<spechash>.so (include/scg_ilqr.h): the LQR / iLQR baseline controllers' two kernels — the
 closed-loop rollout with an affine time-varying state feedback in the loop and iLQR's backward pass — and the PID baseline's rollout
-(include/scg_pid.h, csrc/scg_pid.h), compiled per task config from csrc/scg_ilqr.hip.  The controllers' own settings (Q, R, the prior model's parameters) travel by value: one library serves every
+(include/scg_pid.h, csrc/scg_pid.h) and the LDS-resident backward pass that serves Quadrotor 3D (include/scg_ilqr_wide.h,
+csrc/scg_ilqr_wide.h), compiled per task config from csrc/scg_ilqr.hip.  The controllers' own settings (Q, R, the prior model's parameters) travel by value: one library serves every
 controller config of its task.  The library carries every scg_hip.h entry point as well (_lib.EXPORTS): HipVecEnv(..., ilqr=True)
 drives its handle with it.  No fallback lives here: a system or an env config the library does not serve is an error."""
 import ctypes as C
@@ -13,7 +14,9 @@ SRC = os.path.join(L.CSRC_DIR, 'scg_ilqr.hip')
 HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_ilqr.h'))
 PID_SRC = os.path.join(L.CSRC_DIR, 'scg_pid.h')                    # the PID rollout: included by scg_ilqr.hip
 PID_HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_pid.h'))
-DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [SRC, HEADER, PID_SRC, PID_HEADER]
+WIDE_SRC = os.path.join(L.CSRC_DIR, 'scg_ilqr_wide.h')              # the LDS-resident backward pass: included by scg_ilqr.hip
+WIDE_HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_ilqr_wide.h'))
+DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [SRC, HEADER, PID_SRC, PID_HEADER, WIDE_SRC, WIDE_HEADER]
 PREFIX = 'libscg_ilqr_'
 
 
@@ -81,7 +84,7 @@ _libs = {}
 
 
 def lib_for(cfg):
-    """The bound library (every _lib.EXPORTS symbol + scg_rollout_feedback / scg_ilqr_backward / scg_rollout_pid), built now if missing or stale."""
+    """The bound library (every _lib.EXPORTS symbol + scg_rollout_feedback / scg_ilqr_backward / scg_ilqr_backward_wide / scg_rollout_pid), built now if missing or stale."""
     _, h = L.spec_source(cfg)
     if h in _libs:
         return _libs[h]
@@ -95,6 +98,7 @@ def lib_for(cfg):
         raise L.ScgError(f'{so} was built for another config')
     D.scg_rollout_feedback.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeedbackRollout), C.c_void_p]
     D.scg_ilqr_backward.argtypes = [C.c_void_p, C.POINTER(IlqrModel), C.c_int] + [C.c_void_p] * 9
+    D.scg_ilqr_backward_wide.argtypes = [C.c_void_p, C.POINTER(IlqrModel), C.c_int] + [C.c_void_p] * 9
     D.scg_ilqr_snapshot.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     D.scg_ilqr_restart.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     D.scg_rollout_pid.argtypes = [C.c_void_p, C.c_int, C.POINTER(PidRollout), C.c_void_p]

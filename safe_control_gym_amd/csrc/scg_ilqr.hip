@@ -8,7 +8,8 @@
 //
 // Built only as   hipcc ... -DSCG_SPEC -include <spec header> scg_ilqr.hip   (safe_control_gym_amd/_ilqr.py); the simulator's
 // translation unit is included whole, without any edit to it.  The PID baseline's rollout (scg_pid.h, include/scg_pid.h) is included at
-// the end: one library per task config serves lqr, ilqr and pid.
+// the end: one library per task config serves lqr, ilqr and pid.  So is the LDS-resident backward pass (scg_ilqr_wide.h,
+// include/scg_ilqr_wide.h), which serves Quadrotor 3D as well.
 #include "scg_kernels.hip"
 
 #include "../../include/scg_ilqr.h"
@@ -432,3 +433,4 @@ extern "C" int scg_ilqr_restart(scg_env* env, const void* d_state, void* stream)
 }
 
 #include "scg_pid.h"
+#include "scg_ilqr_wide.h"

@@ -7,14 +7,15 @@
 One env is one problem: its own initial state (and, with randomized_inertial_prop, its own inertial parameters), its own lambda, its
 own accept / reject history.  Per iLQR iteration the device runs ONE `scg_rollout_feedback` launch (the closed loop of every env with
 its current schedule), a handful of elementwise [N] tensor ops (the accept / reject / converged bookkeeping of ilqr.py:117-181), and ONE
-`scg_ilqr_backward` launch masked to the envs that update (include/scg_ilqr.h).  The LQR gain is one small matrix shared by all envs:
+`scg_ilqr_backward` (or, with `wide_backward=True`, `scg_ilqr_backward_wide`) launch masked to the envs that update (include/scg_ilqr.h).  The LQR gain is one small matrix shared by all envs:
 A, B of the prior model at (X_EQ, U_EQ), Euler-discretised, the discrete Riccati equation solved on the host in NumPy.
 
 The one difference from upstream a caller can see: every env's initial state is FIXED for the whole of `learn` (init_states[i], or what
 the env's first reset drew); every iteration restarts from it.  Upstream calls a bare `env.reset()` per iteration and so, with
 randomized_init on, compares costs of different initial states (its shipped configs switch randomized_init off).
 
-Served: `lqr` on all four systems; `ilqr` on CartPole, Quadrotor 1D and 2D (Quadrotor 3D raises NotImplementedError: include/scg_ilqr.h).
+Served: `lqr` on all four systems; `ilqr` on CartPole, Quadrotor 1D and 2D, and with the extension key `wide_backward=True` (the
+LDS-resident backward pass, include/scg_ilqr_wide.h) on Quadrotor 3D as well; without the key Quadrotor 3D raises NotImplementedError.
 The env takes physical actions (normalized_rl_action_space off) and observes its state (cost: quadratic).  No CPU path.
 """
 import ctypes as C
@@ -257,7 +258,10 @@ class iLQR(LQR):
     """Iterative linear quadratic regulator (controllers/lqr/ilqr.py), one independent problem per env."""
 
     def __init__(self, env_func, q_lqr=None, r_lqr=None, discrete_dynamics=True, max_iterations=15, lamb_factor=10, lamb_max=1000,
-                 epsilon=0.01, **kwargs):
+                 epsilon=0.01, wide_backward=False, **kwargs):
+        # wide_backward: an extension key (not in ilqr.yaml).  True: learn runs the LDS-resident backward pass (scg_ilqr_backward_wide),
+        # which serves every system; False: the register-resident one, which does not serve Quadrotor 3D.
+        self.wide_backward = bool(wide_backward)
         self.max_iterations, self.lamb_factor, self.lamb_max, self.epsilon = int(max_iterations), float(lamb_factor), float(lamb_max), float(epsilon)
         super().__init__(env_func, q_lqr=q_lqr, r_lqr=r_lqr, discrete_dynamics=discrete_dynamics, **kwargs)
         self.ite_counter = 0
@@ -271,9 +275,10 @@ class iLQR(LQR):
         self.task_config['done_on_out_of_bound'] = True                 # ilqr.py:61
 
     def _check_system(self):
-        if self.spec.nx == 12:
-            raise NotImplementedError('ilqr does not serve Quadrotor 3D: the backward kernel holds Sm and Ad in registers (12 x 12 each '
-                                      'do not fit) and inverts the Hessian in closed form (nu <= 2); lqr serves it')
+        if self.spec.nx == 12 and not self.wide_backward:
+            raise NotImplementedError('ilqr serves Quadrotor 3D only with wide_backward=True (the LDS-resident backward pass): the default '
+                                      'backward kernel holds Sm and Ad in registers (12 x 12 each do not fit) and inverts the Hessian in '
+                                      'closed form (nu <= 2)')
 
     def model_struct(self):
         from safe_control_gym_amd import _ilqr
@@ -350,7 +355,7 @@ class iLQR(LQR):
             have_best = have_best | accept
             self.history.append(dict(cost=cost.clone(), lamb=lamb.clone(), accept=accept, reject=reject, converged=conv,
                                      active=active, n_steps=n_steps.clone()))
-            venv.ilqr_backward(model, T, b['x'], b['u'], n_steps, lamb, update.to(torch.uint8), gains, ff, unstable)
+            venv.ilqr_backward(model, T, b['x'], b['u'], n_steps, lamb, update.to(torch.uint8), gains, ff, unstable, wide=self.wide_backward)
             ite = torch.where(active & ~finished, ite + 1, ite)
             if bool(finished.all()):                                     # the one host check of the iteration
                 break

@@ -117,7 +117,8 @@ register(idx='cbf', entry_point='safe_control_gym_amd.cbf:CBF', config_entry_poi
 
 # baseline controller ids of the reference (controllers/__init__.py: 'lqr', 'ilqr', 'pid'), batched: one closed-loop launch per rollout,
 # one backward-pass launch per iLQR iteration (lqr.py, csrc/scg_ilqr.hip); 'pid' (pid.py, csrc/scg_pid.h) is the quadrotor-only cascade
-# PID with its integrator state carried inside the launch.  'ilqr' raises NotImplementedError for Quadrotor 3D, 'pid' for anything but
+# PID with its integrator state carried inside the launch.  'ilqr' serves Quadrotor 3D with the extension key wide_backward=True (the
+# LDS-resident backward pass, csrc/scg_ilqr_wide.h) and raises NotImplementedError for it without; 'pid' raises for anything but
 # Quadrotor 2D / 3D.  tools/run_reference_example.py binds the REFERENCE's own registry module, so its ids do not meet these.
 register(idx='lqr', entry_point='safe_control_gym_amd.lqr:LQR', config_entry_point='safe_control_gym_amd.lqr:LQR_DEFAULTS')
 register(idx='ilqr', entry_point='safe_control_gym_amd.lqr:iLQR', config_entry_point='safe_control_gym_amd.lqr:ILQR_DEFAULTS')

@@ -663,7 +663,7 @@ class HipVecEnv(VecEnv):
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_pid(self._h, K, C.byref(io), self._stream()))
 
-    def ilqr_backward(self, model, k_steps, x, u, n_steps, lamb, mask, gains, ff, unstable):
+    def ilqr_backward(self, model, k_steps, x, u, n_steps, lamb, mask, gains, ff, unstable, wide=False):
         """iLQR's backward pass for every env whose mask byte is set, ONE launch (scg_ilqr_backward, include/scg_ilqr.h): `model` an
         _ilqr.IlqrModel, x [K + 1, nx, N] (row n_steps[i] = env i's final observation), u [K, nu, N], n_steps int32 [N], lamb [N],
         mask uint8 [N] or None; gains [K, nu, nx, N] and ff [K, nu, N] are updated in place, unstable uint8 [N] is set where the
@@ -679,9 +679,14 @@ class HipVecEnv(VecEnv):
             if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
                 raise ValueError(f'{k} must be a contiguous {list(shape)} {dt} tensor on the env device')
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        entry = self._lib.scg_ilqr_backward_wide if wide else self._lib.scg_ilqr_backward
         with torch.cuda.device(self.device):
-            self._chk(self._lib.scg_ilqr_backward(self._h, C.byref(model), K, p(x), p(u), p(n_steps), p(lamb), p(mask), p(gains), p(ff),
-                                                  p(unstable), self._stream()))
+            self._chk(entry(self._h, C.byref(model), K, p(x), p(u), p(n_steps), p(lamb), p(mask), p(gains), p(ff), p(unstable), self._stream()))
+
+    def ilqr_backward_wide(self, model, k_steps, x, u, n_steps, lamb, mask, gains, ff, unstable):
+        """ilqr_backward's arguments and rules through scg_ilqr_backward_wide (include/scg_ilqr_wide.h): the recursion's matrices in LDS,
+        a Jacobi eigen-solve for four inputs.  Serves every system, Quadrotor 3D included."""
+        self.ilqr_backward(model, k_steps, x, u, n_steps, lamb, mask, gains, ff, unstable, wide=True)
 
     def ilqr_snapshot(self):
         """Every env's raw simulator state as a device tensor [ns, N] (scg_ilqr_snapshot); ilqr_restart(snapshot) puts it back and zeroes
