@@ -39,6 +39,11 @@ def configs():
         for seed in SPEC_SEEDS:
             env_id, c = fuzz_config(system, seed)
             out.append((env_id, dict(c, _no_rk4=True)))
+    # tests/test_gpu_extreme_states.py: the four cases it also runs specialised, each in its one dtype
+    from tests import extreme_state_cases as X
+    for name, tag in X.SPECIALISED:
+        env_id, c = X.load_config(X.CASE_BY_NAME[name])
+        out.append((env_id, dict(c, _no_rk4=True, _dtypes=(tag,))))
     return out
 
 
@@ -50,13 +55,15 @@ def main():
     todo = {}
     for task, cfg in configs():
         no_rk4 = cfg.pop('_no_rk4', False)
+        dtypes = [{'f32': _lib.F32, 'f64': _lib.F64}[t] for t in cfg.pop('_dtypes', ('f32', 'f64'))]
+        auto_reset = cfg.pop('auto_reset', True)                # (HipVecEnv's own argument, not an EnvSpec key)
         variants = [cfg]
         if not no_rk4 and not cfg.get('disturbances') and not cfg.get('adversary_disturbance'):
             variants.append(dict(cfg, integrator='rk4'))
         for c in variants:
-            for dt in (_lib.F32, _lib.F64):
+            for dt in dtypes:
                 try:
-                    cc, _ = EnvSpec(task, dict(c)).to_c_config(1, dt, 0)
+                    cc, _ = EnvSpec(task, dict(c)).to_c_config(1, dt, 0, 0, auto_reset)
                 except Exception:                               # noqa: BLE001  (a variant the config layer rejects)
                     continue
                 _, h = _lib.spec_source(cc)
