@@ -32,14 +32,8 @@ class DdpgNoise(C.Structure):
                 ('std_inc', C.c_double), ('d_x_prev', C.c_void_p), ('d_x_next', C.c_void_p), ('d_calls', C.c_void_p), ('d_pending', C.c_void_p)]
 
 
-class DdpgRing(C.Structure):
-    _fields_ = [('d_obs', C.c_void_p), ('d_act', C.c_void_p), ('d_rew', C.c_void_p), ('d_next_obs', C.c_void_p), ('d_mask', C.c_void_p),
-                ('capacity', C.c_int32), ('d_pos', C.c_void_p), ('d_size_f', C.c_void_p), ('d_size_i32', C.c_void_p), ('d_counter', C.c_void_p)]
-
-
-def supported(obs_dim, hidden, act_dim, activation):
-    return (1 <= act_dim <= 4 and obs_dim >= 1 and obs_dim + act_dim < 32 and hidden % 32 == 0 and 32 <= hidden <= 128
-            and activation in ACTS)
+DdpgRing = _shapelib.Ring
+supported = _shapelib.supported
 
 
 def source_hash():

@@ -24,17 +24,9 @@ class SacArgs(C.Structure):
                 ('d_workspace', C.c_void_p), ('d_stats', C.c_void_p), ('d_stats_acc', C.c_void_p), ('phases', C.c_int32)]
 
 
-class SacRing(C.Structure):
-    _fields_ = [('d_obs', C.c_void_p), ('d_act', C.c_void_p), ('d_rew', C.c_void_p), ('d_next_obs', C.c_void_p), ('d_mask', C.c_void_p),
-                ('capacity', C.c_int32), ('d_pos', C.c_void_p), ('d_size_f', C.c_void_p), ('d_size_i32', C.c_void_p), ('d_counter', C.c_void_p)]
-
-
+SacRing = _shapelib.Ring
+supported = _shapelib.supported
 ACTOR_GRAD, CRITIC_GRAD, FINISH, ALL = 1, 2, 4, 7
-
-
-def supported(obs_dim, hidden, act_dim, activation):
-    return (1 <= act_dim <= 4 and obs_dim >= 1 and obs_dim + act_dim < 32 and hidden % 32 == 0 and 32 <= hidden <= 128
-            and activation in ACTS)
 
 
 def source_hash():

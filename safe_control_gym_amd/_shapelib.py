@@ -1,12 +1,26 @@
 """What the builders of the per-network-shape libraries (_learn, _sac, _ddpg) have in common: the source digest that stamps a
-library, the "current? else hipcc" build, and the load that refuses a stale or mis-shaped library.  Plain functions; each module
-keeps its sources (SRC, DEPS), its ctypes structs and bindings, and its public names."""
+library, the "current? else hipcc" build, and the load that refuses a stale or mis-shaped library — and what the two off-policy
+libraries (_sac, _ddpg) share beyond that: the replay-ring struct and the shapes they serve.  Each module keeps its sources (SRC,
+DEPS), its argument structs and bindings, and its public names."""
 import ctypes as C
 import hashlib
 import os
 import subprocess
 
 from safe_control_gym_amd import _lib as L
+
+
+class Ring(C.Structure):
+    """scg_sac_ring / scg_ddpg_ring (include/scg_sac.h, scg_ddpg.h: the same fields): the replay ring a collector's push writes."""
+    _fields_ = [('d_obs', C.c_void_p), ('d_act', C.c_void_p), ('d_rew', C.c_void_p), ('d_next_obs', C.c_void_p), ('d_mask', C.c_void_p),
+                ('capacity', C.c_int32), ('d_pos', C.c_void_p), ('d_size_f', C.c_void_p), ('d_size_i32', C.c_void_p), ('d_counter', C.c_void_p)]
+
+
+def supported(obs_dim, hidden, act_dim, activation):
+    """The network shapes the off-policy libraries (_sac, _ddpg: the wide-tile passes of csrc/scg_wide.h) serve."""
+    from safe_control_gym_amd._learn import ACTS
+    return (1 <= act_dim <= 4 and obs_dim >= 1 and obs_dim + act_dim < 32 and hidden % 32 == 0 and 32 <= hidden <= 128
+            and activation in ACTS)
 
 
 def source_hash(deps):

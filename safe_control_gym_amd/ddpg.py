@@ -19,8 +19,11 @@ MI355X-first differences (as sac.py): the replay ring lives in HBM and is filled
 gradient step is the fused library (csrc/scg_ddpg.hip) replayed as a HIP graph, and a vector step of the collector is three
 library launches + the env kernel, the noise process continued across the env batch on the device (an affine scan in float64).
 With several updates owed per vector step, `_since_update` / extra['updates_per_step'] work as in sac.py.
+
+What DDPG shares with SAC — the replay ring, the flat-parameter bookkeeping, the collectors, train_step / learn and the checkpoint
+format — lives in offpolicy.py (FlatAgent, OffPolicyTrainer); this module holds the noise processes, the networks, the config, the
+losses, the update paths and the hooks in which DDPG differs.
 """
-import time
 import warnings
 from copy import deepcopy
 from dataclasses import dataclass, field
@@ -30,8 +33,9 @@ import torch
 import torch.nn as nn
 
 from safe_control_gym_amd import parallel
+from safe_control_gym_amd.offpolicy import DeviceReplay, FlatAgent, OffPolicyConfig, OffPolicyTrainer  # noqa: F401 (DeviceReplay: re-exported)
 from safe_control_gym_amd.ppo import MLP
-from safe_control_gym_amd.sac import DeviceReplay, MLPQFunction
+from safe_control_gym_amd.sac import MLPQFunction
 
 
 # ---------------------------------------------------------------------------------------------------------------- noise
@@ -141,7 +145,7 @@ class MLPActorCritic(nn.Module):
 
 
 @dataclass
-class DDPGConfig:
+class DDPGConfig(OffPolicyConfig):
     # names and defaults of controllers/ddpg/ddpg.yaml
     hidden_dim: int = 256
     activation: str = 'relu'
@@ -158,24 +162,20 @@ class DDPGConfig:
     max_buffer_size: int = 1000000
     extra: dict = field(default_factory=dict)
 
-    @classmethod
-    def from_dict(cls, d):
-        known = {k: v for k, v in d.items() if k in cls.__dataclass_fields__}
-        return cls(**known, extra={k: v for k, v in d.items() if k not in cls.__dataclass_fields__})
-
 
 # ---------------------------------------------------------------------------------------------------------------- agent
-class DDPGAgent:
+class DDPGAgent(FlatAgent):
+    OPTIMIZERS = ('actor_opt', 'critic_opt')
+    LOSS_NAMES = ('policy_loss', 'critic_loss')
+    ACTOR_KIND = 'ddpg'
+    DETERMINISTIC_ACT = 'act'
+
     def __init__(self, obs_dim, act_dim, low, high, cfg: DDPGConfig, device):
         self.cfg, self.obs_dim, self.act_dim = cfg, obs_dim, act_dim
         dev = torch.device(device)
         low = torch.as_tensor(low, dtype=torch.float32, device=dev).reshape(-1)
         high = torch.as_tensor(high, dtype=torch.float32, device=dev).reshape(-1)
-        self.ac = MLPActorCritic(obs_dim, act_dim, low, high, [cfg.hidden_dim] * 2, cfg.activation).to(dev)
-        parallel.broadcast_parameters([self.ac])
-        self.ac_targ = deepcopy(self.ac)
-        for p in self.ac_targ.parameters():
-            p.requires_grad = False
+        self._adopt(MLPActorCritic(obs_dim, act_dim, low, high, [cfg.hidden_dim] * 2, cfg.activation).to(dev))
         # Fused gradient step (csrc/scg_ddpg.hip): the whole DDPGAgent.update as 8 launches on flat parameter vectors, replayed as a HIP
         # graph.  Chosen here, visibly: GPU runs of shapes the library serves; everything else is the eager PyTorch update below.
         from safe_control_gym_amd import _ddpg
@@ -193,19 +193,8 @@ class DDPGAgent:
                 _ddpg.check(D, D.scg_ddpg_prepare())
         self.actor_opt = torch.optim.Adam(self.ac.actor.parameters(), cfg.actor_lr)
         self.critic_opt = torch.optim.Adam(self.ac.q.parameters(), cfg.critic_lr)
-        self._ab = self._cb = None
 
     # ---- eager update (ddpg_utils.py:96-121)
-    def _reduce(self, params, attr):
-        if parallel.world_size() > 1:
-            b = getattr(self, attr)
-            if b is None:
-                b = parallel.FlatBucket(params)
-                setattr(self, attr, b)
-            b.pack()
-            b.all_reduce_mean()
-            b.unpack()
-
     def compute_policy_loss(self, batch):
         obs = batch['obs']
         return -self.ac.q(obs, self.ac.actor(obs)).mean()
@@ -238,51 +227,14 @@ class DDPGAgent:
         """All trainable tensors as views of ONE flat vector [actor | q] (+ target vector, gradient, Adam moments); the torch
         modules keep working on the views (acting, evaluation, checkpoints)."""
         from safe_control_gym_amd._learn import MlpLayout
-        dev = low.device
 
         def order(ac):
             return [p for f in ac.actor.net.fcs for p in (f.weight, f.bias)] + [p for f in ac.q.q_net.fcs for p in (f.weight, f.bias)]
         if len(self.ac.actor.net.fcs) != 3 or len(self.ac.q.q_net.fcs) != 3:
             raise ValueError('the fused DDPG update serves two hidden layers')
-        params = order(self.ac)
-        flat = torch.cat([p.data.reshape(-1) for p in params]).contiguous()
-        offs, off = [], 0
-        for p in params:
-            offs.append(off)
-            p.data = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        n = off
-        targ = torch.empty(n, device=dev)
-        off = 0
-        for p in order(self.ac_targ):
-            targ[off:off + p.numel()].copy_(p.data.reshape(-1))
-            p.data = targ[off:off + p.numel()].view_as(p)
-            off += p.numel()
+        fl, offs = self._flat_views(order(self.ac), order(self.ac_targ), low, high)
         lay = lambda k: MlpLayout(*offs[k:k + 6])      # noqa: E731
-        z = lambda: torch.zeros(n, device=dev)          # noqa: E731
-        return {'p': flat, 'targ': targ, 'g': z(), 'm': z(), 'v': z(), 'steps': torch.zeros(2, device=dev), 'n': n, 'n_actor': offs[6],
-                'actor': lay(0), 'q': lay(6), 'low': [float(x) for x in low], 'high': [float(x) for x in high],
-                'counter': torch.zeros(1, dtype=torch.int32, device=dev), 'seed': int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF}
-
-    def actor_struct(self):
-        """The scg_actor (_lib.Actor, include/scg_actor_rollout.h) of the deterministic actor for the fused rollout (HipVecEnv.rollout_actor):
-        the flat vector's actor layout and the bounds cached for scg_ddpg_act.  Fused agents only."""
-        from safe_control_gym_amd import _lib as L
-        if not self.use_fused:
-            raise L.ScgError('actor_struct needs the fused agent (the flat parameter vector)')
-        fl, lay = self._flat, self._flat['actor']
-        pad = [0.0] * (4 - self.act_dim)
-        return L.Actor(d_params=fl['p'].data_ptr(), W1=lay.W1, b1=lay.b1, W2=lay.W2, b2=lay.b2, W3=lay.W3, b3=lay.b3, hidden=self.cfg.hidden_dim,
-                       activation=L.POLICY_ACTS[self.cfg.activation], kind=L.ACTOR_KINDS['ddpg'],
-                       act_low=(L.C.c_float * 4)(*(fl['low'] + pad)), act_high=(L.C.c_float * 4)(*(fl['high'] + pad)))
-
-    def act_bounds(self):
-        import ctypes as C
-        fl = self._flat
-        if '_act_bounds' not in fl:
-            pad = [0.0] * (4 - self.act_dim)
-            fl['_act_bounds'] = ((C.c_float * 4)(*(fl['low'] + pad)), (C.c_float * 4)(*(fl['high'] + pad)))
-        return fl['_act_bounds']
+        return dict(fl, n_actor=offs[6], actor=lay(0), q=lay(6))
 
     def _fused_args(self, buffer, batch_size, idx=None):
         import ctypes as C
@@ -330,19 +282,7 @@ class DDPGAgent:
                     self.fused_step(F, n_updates)
             F['graphs'][n_updates] = g
         g.replay()
-        if lazy:
-            return {'stats_dev': F['acc'], 'stats_updates': n_updates}
-        st = (F['acc'] / n_updates).tolist()
-        return {'policy_loss': st[0], 'critic_loss': st[1]}
-
-    def update_from_buffer(self, buffer, batch_size, n_updates, lazy=False):
-        if self.use_fused:
-            return self._update_fused(buffer, batch_size, n_updates, lazy=lazy)
-        acc = None
-        for _ in range(n_updates):
-            res = self.update(buffer.sample(batch_size))
-            acc = res if acc is None else {k: acc[k] + v for k, v in res.items()}
-        return {k: v / n_updates for k, v in acc.items()}
+        return self._fused_stats(F, n_updates, lazy)
 
     # ---- acting
     @torch.no_grad()
@@ -361,71 +301,12 @@ class DDPGAgent:
                                           x.data_ptr(), x.shape[0], out.data_ptr(), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
         return out
 
-    def deterministic_policy(self):
-        if getattr(self, '_det_policy', None) is None:
-            agent = self
-
-            class _Det:
-                ac = agent.ac
-
-                @staticmethod
-                def act(obs):
-                    return agent.act(obs)
-            self._det_policy = _Det()
-        return self._det_policy
-
-    # ---- checkpoints: the reference's keys (ddpg_utils.py:58-72); the fused Adam moments travel in torch.optim's layout
-    def _opt_groups(self):
-        return ((self.actor_opt, 0), (self.critic_opt, 1))
-
-    def _flat_offset(self, p):
-        fl = self._flat['p']
-        return (p.data_ptr() - fl.data_ptr()) // fl.element_size()
-
-    def state_dict(self):
-        if self._flat is not None:
-            fl = self._flat
-            steps = fl['steps'].tolist()
-            for opt, which in self._opt_groups():
-                if steps[which] <= 0:
-                    continue
-                for p in opt.param_groups[0]['params']:
-                    o, k = self._flat_offset(p), p.numel()
-                    opt.state[p] = {'step': torch.tensor(float(steps[which])), 'exp_avg': fl['m'][o:o + k].view_as(p).clone(),
-                                    'exp_avg_sq': fl['v'][o:o + k].view_as(p).clone()}
-        sd = {'ac': self.ac.state_dict(), 'ac_targ': self.ac_targ.state_dict(), 'actor_opt': self.actor_opt.state_dict(),
-              'critic_opt': self.critic_opt.state_dict()}
-        if self._flat is not None:
-            sd['flat_adam'] = {'counter': self._flat['counter'].clone()}
-        return sd
-
     def load_state_dict(self, sd, with_optimizers=True):
+        """The reference's keys (ddpg_utils.py:58-72), strictly: upstream's state dict has no bounds, and neither has MLPActor's."""
         self.ac.load_state_dict(sd['ac'])
         self.ac_targ.load_state_dict(sd['ac_targ'])
         if with_optimizers:
-            self.actor_opt.load_state_dict(sd['actor_opt'])
-            self.critic_opt.load_state_dict(sd['critic_opt'])
-            for opt, _ in self._opt_groups():
-                for st in opt.state.values():
-                    if torch.is_tensor(st.get('step')):
-                        st['step'] = st['step'].cpu()
-            if self._flat is not None:      # in place: captured graphs alias the flat buffers
-                fl = self._flat
-                for opt, which in self._opt_groups():
-                    n_steps = 0.0
-                    for p in opt.param_groups[0]['params']:
-                        st = opt.state.get(p)
-                        o, k = self._flat_offset(p), p.numel()
-                        if not st:
-                            fl['m'][o:o + k].zero_()
-                            fl['v'][o:o + k].zero_()
-                            continue
-                        fl['m'][o:o + k].copy_(st['exp_avg'].reshape(-1))
-                        fl['v'][o:o + k].copy_(st['exp_avg_sq'].reshape(-1))
-                        n_steps = float(st['step'])
-                    fl['steps'][which] = n_steps
-                for k, t in sd.get('flat_adam', {}).items():
-                    fl[k].copy_(t.to(fl[k].device))
+            self._load_optimizers(sd)
 
 
 # ---------------------------------------------------------------------------------------------------------------- device noise
@@ -474,217 +355,66 @@ class DeviceNoise:
 
 
 # ---------------------------------------------------------------------------------------------------------------- controller core
-class DDPG:
-    """DDPG.train_step / learn on a HipVecEnv (ddpg.py:164-341)."""
+class DDPG(OffPolicyTrainer):
+    """DDPG.train_step / learn on a HipVecEnv (ddpg.py:164-341): OffPolicyTrainer with the actor's action plus the noise process —
+    the reference's on the host (NumPy draws) for the PyTorch collector, which therefore is not captured in a HIP graph, DeviceNoise
+    for the fused one (scg_ddpg_noisy_act + the env kernel + scg_ddpg_push)."""
+    AGENT = DDPGAgent
 
     def __init__(self, env, cfg: DDPGConfig, seed=0):
-        self.env, self.cfg = env, cfg
-        self.device = env.device
-        if env.dtype != torch.float32:
-            raise ValueError('the DDPG collector runs on float32 environments')
-        from safe_control_gym_amd.normalization import BaseNormalizer, MeanStdNormalizer, RewardStdNormalizer
-        x = cfg.extra
-        self.obs_normalizer = (MeanStdNormalizer((env.spec.obs_dim,), self.device, clip=x.get('clip_obs', 10.0)) if x.get('norm_obs')
-                               else BaseNormalizer())
-        self.reward_normalizer = (RewardStdNormalizer(cfg.gamma, self.device, clip=x.get('clip_reward', 10.0)) if x.get('norm_reward')
-                                  else BaseNormalizer())
-        self._normalise = bool(x.get('norm_obs') or x.get('norm_reward'))
-        if x.get('norm_reward'):
-            self.reward_normalizer.ret = torch.zeros(env.num_envs, dtype=torch.float64, device=self.device)
-        spec = env.spec
-        self.N, self.obs_dim, self.act_dim = env.num_envs, spec.obs_dim, spec.nu
-        rank = torch.distributed.get_rank() if parallel.world_size() > 1 else 0
-        torch.manual_seed(seed + 7919 * rank)
-        np.random.seed(seed + 7919 * rank)
-        self.low = torch.as_tensor(spec.action_space.low, dtype=torch.float32, device=self.device)
-        self.high = torch.as_tensor(spec.action_space.high, dtype=torch.float32, device=self.device)
-        self.agent = DDPGAgent(self.obs_dim, self.act_dim, self.low, self.high, cfg, self.device)
-        self.buffer = DeviceReplay(cfg.max_buffer_size, self.obs_dim, self.act_dim, self.device)
-        self.obs = self.obs_normalizer(env.reset_tensors()).clone()
-        self.total_steps = 0
-        self._since_update = 0
-        # fused collector (scg_ddpg_noisy_act + the env kernel + scg_ddpg_push, replayed as one HIP graph per phase): the fused agent and
-        # no running normalisers; extra['fused_collect'] = False keeps the PyTorch collector with the host-side noise process
-        self._fused_collect = bool(self.agent.use_fused and not self._normalise and cfg.extra.get('fused_collect', True))
-        # evaluation as ONE scg_rollout_actor launch: set by the controller's extension key `fused_rollout` (controllers.DDPG)
-        self._fused_rollout = False
-        self._graph_collect = self.device.type == 'cuda' and bool(cfg.extra.get('graph_collect', cfg.extra.get('cuda_graphs', True)))
-        self._collect_graphs = {}
+        super().__init__(env, cfg, seed)
         self.noise_process = None
         if cfg.random_process:
             self.noise_process = (DeviceNoise(cfg.random_process, self.act_dim, self.device) if self._fused_collect
                                   else make_action_noise_process(cfg.random_process, self.act_dim))
-        if self._fused_collect:
-            self._act = torch.zeros(self.N, self.act_dim, device=self.device)
-            self._collect_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
 
-    def uniform_action(self):
-        """The warm-up's action_space.sample() per env (ddpg.py:276-277), for the PyTorch collector."""
-        return self.low + (self.high - self.low) * torch.rand(self.N, self.act_dim, device=self.device)
-
-    def _policy_struct(self, deterministic=True):
-        """The actor for the fused evaluation (ppo.evaluate(policy=)): deterministic only."""
-        return self.agent.actor_struct()
+    def _seed(self, seed):
+        super()._seed(seed)
+        np.random.seed(seed)
 
     def reset_noise(self):
         """noise_process.reset_states() of the reference's DDPG.reset() in training mode (ddpg.py:100-102)."""
         if self.noise_process is not None:
             self.noise_process.reset_states()
 
-    # ---- one vectorised env step into the replay ring (ddpg.py:273-316)
-    @torch.no_grad()
-    def _collect_body(self, warm):
-        if self._fused_collect:
-            return self._collect_body_fused(warm)
-        if warm:
-            act = self.uniform_action()
-        else:
-            act = self.agent.ac.act(self.obs)
-            if self.noise_process is not None:      # one sample() per env, in env order (ddpg.py:283-286)
-                nz = np.stack([self.noise_process.sample() for _ in range(self.N)])
-                act = (act.double() + torch.as_tensor(nz, device=self.device)).float()
-        out = self.env.step_tensors(act)
-        done = out.done.bool()
-        trunc = (out.flags & 1).bool() & done
-        if self._normalise:
-            self.obs_normalizer.unset_read_only()
-            obs_n = self.obs_normalizer(out.obs)
-            rew = self.reward_normalizer(out.reward, done)
-            term_n = self.obs_normalizer(out.terminal_obs, mask=trunc)
-        else:
-            obs_n, rew, term_n = out.obs, out.reward, out.terminal_obs
-        next_obs = torch.where(trunc[:, None], term_n, obs_n)
-        mask = torch.where(trunc, torch.ones_like(out.reward), 1.0 - done.to(torch.float32))
-        self.buffer.push_device(self.obs, act, rew, next_obs, mask)
-        self.obs.copy_(obs_n)
+    def _explore(self):
+        act = self.agent.ac.act(self.obs)
+        if self.noise_process is not None:      # one sample() per env, in env order (ddpg.py:283-286)
+            nz = np.stack([self.noise_process.sample() for _ in range(self.N)])
+            act = (act.double() + torch.as_tensor(nz, device=self.device)).float()
+        return act
 
-    def _collect_body_fused(self, warm, eps_in=None):
-        """eps_in: [N][act_dim] N(0, 1) draws of the noise in place of the in-kernel Philox ones (replaying a recorded run)."""
+    def _fused_act(self, warm, eps_in, st):
         import ctypes as C
         from safe_control_gym_amd import _ddpg
-        ag, buf = self.agent, self.buffer
-        fl = ag._flat
         D = _ddpg.lib(self.obs_dim, self.cfg.hidden_dim, self.act_dim, self.cfg.activation)
-        lo, hi = ag.act_bounds()
-        p = lambda t: t.data_ptr()                      # noqa: E731
-        if getattr(self, '_ring_of', None) is not buf:
-            self._ring = _ddpg.DdpgRing(d_obs=p(buf.obs), d_act=p(buf.act), d_rew=p(buf.rew), d_next_obs=p(buf.next_obs), d_mask=p(buf.mask),
-                                        capacity=buf.capacity, d_pos=p(buf.pos_t), d_size_f=p(buf.size_t), d_size_i32=p(buf.size_i32),
-                                        d_counter=p(self._collect_counter))
-            self._ring_of = buf
-        if self.N > buf.capacity:
-            raise ValueError('replay capacity smaller than one vectorised step')
+        fl, (lo, hi) = self.agent._flat, self.agent.act_bounds()
         nz = C.byref(self.noise_process.struct) if self.noise_process is not None else None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _ddpg.check(D, D.scg_ddpg_noisy_act(p(fl['p']), C.byref(fl['actor']), lo, hi, p(self.obs), self.N, fl['seed'], p(self._collect_counter),
-                                                int(bool(warm)), nz, p(eps_in) if eps_in is not None else None, p(self._act), st))
-            out = self.env.step_tensors(self._act)
-            _ddpg.check(D, D.scg_ddpg_push(C.byref(self._ring), nz, p(self.obs), p(self._act), p(out.reward), p(out.obs), p(out.terminal_obs),
-                                           p(out.done), p(out.flags), self.N, st))
+        p = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
+        _ddpg.check(D, D.scg_ddpg_noisy_act(p(fl['p']), C.byref(fl['actor']), lo, hi, p(self.obs), self.N, fl['seed'], p(self._collect_counter),
+                                            int(bool(warm)), nz, p(eps_in), p(self._act), st))
 
-    def _collect(self, warm):
-        """Eager, or one HIP-graph replay per vector step (captured after two eager steps of each phase, as sac.SAC._collect)."""
-        if not self._graph_collect or not self._fused_collect:
-            self._collect_body(warm)
-            return
-        key = (bool(warm), getattr(self.env, 'seed_epoch', 0), id(self.buffer))
-        st = self._collect_graphs.setdefault(key, {'eager': 0, 'g': None})
-        if st['g'] is None:
-            if st['eager'] < 2:
-                st['eager'] += 1
-                self._collect_body(warm)
-                return
-            torch.cuda.current_stream(self.device).synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._collect_body(warm)
-            st['g'] = g
-        st['g'].replay()
+    def _fused_push(self, out, st):
+        import ctypes as C
+        from safe_control_gym_amd import _ddpg
+        D = _ddpg.lib(self.obs_dim, self.cfg.hidden_dim, self.act_dim, self.cfg.activation)
+        nz = C.byref(self.noise_process.struct) if self.noise_process is not None else None
+        p = lambda t: t.data_ptr()                      # noqa: E731
+        _ddpg.check(D, D.scg_ddpg_push(C.byref(self._ring), nz, p(self.obs), p(self._act), p(out.reward), p(out.obs), p(out.terminal_obs),
+                                       p(out.done), p(out.flags), self.N, st))
 
-    def train_step(self, lazy=False):
-        cfg = self.cfg
-        t0 = time.perf_counter()
-        self._collect(self.total_steps < cfg.warm_up_steps)
-        self.buffer.advance_host(self.N)
-        world = parallel.world_size()
-        self.total_steps += self.N * world
-        self._since_update += self.N * world
-        results = {}
-        if self.total_steps > cfg.warm_up_steps and self._since_update >= cfg.train_interval:
-            # as sac.SAC.train_step: the reference's ratio of one gradient step per env step; `updates_per_step` caps it
-            n_updates = int(cfg.extra.get('updates_per_step', self._since_update))
-            self._since_update = 0
-            results = self.agent.update_from_buffer(self.buffer, cfg.train_batch_size, n_updates, lazy=lazy)
-            results['updates'] = n_updates
-        results.update({'step': self.total_steps, 'elapsed_time': time.perf_counter() - t0})
-        return results
+    # ---- checkpoints: the NumPy generator (the host noise draws) and the noise process travel too (ddpg.py:116-162)
+    def _save_extra(self, state):
+        state['random_state']['numpy'] = np.random.get_state()
+        if self.noise_process is not None:
+            state['noise_process'] = self.noise_process.state_dict()
 
-    # ---- checkpoint / resume (ddpg.py:116-162: same keys)
-    def save(self, path, training=True, save_buffer=False):
-        import os
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        state = {'agent': self.agent.state_dict(), 'obs_normalizer': self.obs_normalizer.state_dict(),
-                 'reward_normalizer': self.reward_normalizer.state_dict()}
-        for name, nz in (('obs', self.obs_normalizer), ('reward', self.reward_normalizer)):
-            if hasattr(nz, 'rms'):              # (as sac.SAC.save: upstream's state dict drops the count, and the running returns)
-                state[f'{name}_normalizer_count'] = float(nz.rms.count)
-        if getattr(self.reward_normalizer, 'ret', None) is not None:
-            state['reward_normalizer_ret'] = self.reward_normalizer.ret.cpu()
-        if training:
-            state.update({'total_steps': self.total_steps, 'since_update': self._since_update, 'obs': self.obs.cpu(),
-                          'random_state': {'torch': torch.get_rng_state(), 'numpy': np.random.get_state(),
-                                           'torch_cuda': torch.cuda.get_rng_state(self.device) if self.device.type == 'cuda' else None},
-                          'env_random_state': self.env.get_env_random_state()})
-            if self._fused_collect:
-                state['collect_counter'] = int(self._collect_counter.item())
-            if save_buffer:
-                state['buffer'] = self.buffer.state_dict()
-            if self.noise_process is not None:
-                state['noise_process'] = self.noise_process.state_dict()
-        torch.save(state, path)
-
-    def load(self, path, training=True):
-        state = torch.load(path, map_location=self.device, weights_only=False)
-        self.agent.load_state_dict(state['agent'], with_optimizers=training)
-        for name, nz in (('obs', self.obs_normalizer), ('reward', self.reward_normalizer)):
-            if state.get(f'{name}_normalizer') and hasattr(nz, 'rms'):
-                nz.load_state_dict(state[f'{name}_normalizer'])
-                if f'{name}_normalizer_count' in state:
-                    nz.rms.count.fill_(state[f'{name}_normalizer_count'])
-        if 'reward_normalizer_ret' in state and getattr(self.reward_normalizer, 'ret', None) is not None:
-            self.reward_normalizer.ret.copy_(state['reward_normalizer_ret'].to(self.device))       # in place
-        if training and 'total_steps' in state:
-            self.total_steps = int(state['total_steps'])
-            self._since_update = int(state.get('since_update', 0))
-            if 'obs' in state:
-                self.obs.copy_(state['obs'].to(self.device))
-            if self._fused_collect and 'collect_counter' in state:
-                self._collect_counter.fill_(int(state['collect_counter']))
-            if 'env_random_state' in state:
-                self.env.set_env_random_state(state['env_random_state'])
-            rs = state.get('random_state')
-            if rs:
-                torch.set_rng_state(rs['torch'].cpu())
-                if rs.get('numpy') is not None:
-                    np.random.set_state(rs['numpy'])
-                if rs.get('torch_cuda') is not None and self.device.type == 'cuda':
-                    torch.cuda.set_rng_state(rs['torch_cuda'].cpu(), self.device)
-            if 'buffer' in state:
-                self.buffer.load_state_dict(state['buffer'])
-            if self.noise_process is not None and 'noise_process' in state:
-                self.noise_process.load_state_dict(state['noise_process'])
-        return state
-
-    def learn(self, max_env_steps=None, log=None):
-        max_env_steps = max_env_steps or self.cfg.max_env_steps
-        hist = []
-        while self.total_steps < max_env_steps:
-            res = self.train_step()
-            hist.append(res)
-            if log:
-                log(res)
-        return hist
+    def _load_extra(self, state):
+        rs = state.get('random_state') or {}
+        if rs.get('numpy') is not None:
+            np.random.set_state(rs['numpy'])
+        if self.noise_process is not None and 'noise_process' in state:
+            self.noise_process.load_state_dict(state['noise_process'])
 
 
 __all__ = ['DDPG', 'DDPGAgent', 'DDPGConfig', 'DeviceNoise', 'GaussianProcess', 'LinearSchedule', 'OrnsteinUhlenbeckProcess',
