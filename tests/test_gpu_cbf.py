@@ -75,6 +75,20 @@ def _policy(dev, det, scale=1.0, logstd=None):
     return flat, pol, _cbf.actor_ptrs_of_policy(pol)
 
 
+def _actor_module(flat, dev):
+    """The ppo.MLPActor whose parameters are `flat` (the layout _policy packs)."""
+    from safe_control_gym_amd.ppo import MLPActor
+    m = MLPActor(4, 1, [HIDDEN, HIDDEN], ACT).to(dev)
+    tensors = [t for fc in m.pi_net.fcs for t in (fc.weight, fc.bias)] + [m.logstd]
+    at = 0
+    with torch.no_grad():
+        for t in tensors:
+            t.copy_(flat[at:at + t.numel()].view_as(t))
+            at += t.numel()
+    assert at == flat.numel()
+    return m
+
+
 def _bufs(env, k):
     n, nobs, nu = env.num_envs, env.spec.obs_dim, env.spec.nu
     f = dict(device=env.device, dtype=torch.float32)
@@ -181,6 +195,13 @@ def test_rollout_rows_equal_certify_and_the_env_step_is_untouched(normalized, de
     _assert_bits(p['act'][0], o['act'][0], 'act[0]')
     _assert_bits(p['logp'][0], o['logp'][0], 'logp[0]')
     _assert_bits(p['obs'][0], o['obs'][0], 'obs[0]')
+    # ... and on every step: the float64 actor on the recorded observation + sigma x the host Philox model's channel-5 draw at the
+    # env's counters (one reset: episode 0, step 0; auto-resets followed), the log-probability the float64 Gaussian's
+    from tests import philox_model as pm
+    from tests import test_gpu_rollout_noise as RN
+    start = (np.zeros(n, np.int64), np.zeros(n, np.int64), np.arange(n))
+    RN.check_actor('scg_rollout_cbf', _actor_module(flat, env.device), o['obs'][:k], o['act'], o['logp'], det,
+                   *RN.model_draws(o, start, pm.CH_POLICY, 1, seed=seed))
     if det:                                             # the mean: no noise in the action
         flat2, pol2, actor2 = _policy(env.device, True, scale=scale_out, logstd=2.0)
         env4 = _env(n, seed=seed, normalized_rl_action_space=normalized)

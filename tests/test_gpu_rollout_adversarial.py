@@ -113,38 +113,28 @@ def test_env_trajectory_is_bit_exact_against_step_sequence(over, n_adv, epw, wpw
 
 @pytest.mark.parametrize('n_adv', [1, 3])
 def test_actions_and_log_probs_against_pytorch_actors(n_adv):
-    from safe_control_gym_amd.ppo import normal_log_prob
+    from tests import philox_model as pm
+    from tests import test_gpu_rollout_noise as RN
     env = _env(G.ADV_DYNAMICS, n_adv)
     agent, advs = _actors(env, n_adv, seed=1)
     idx = _groups(N, n_adv) if n_adv > 1 else np.zeros(N, dtype=np.int32)
     sel = torch.as_tensor(idx, device=env.device, dtype=torch.long)
-    nobs, ad = env.spec.obs_dim, env.spec.adversary_dim
+    nu, ad = env.spec.nu, env.spec.adversary_dim
 
-    def adv_mean_logstd(x):                     # each env's own adversary on rows [t][env]
-        ms, ls = zip(*[a(x) for a in advs])
-        m = torch.stack(ms).gather(0, sel.view(1, 1, N, 1).expand(1, x.shape[0], N, ad))[0]
-        s = torch.stack(ls)[sel].view(1, N, ad)
-        return m, s
-    # deterministic on both sides: the actors' means on the stored observations
-    env.reset_tensors()
-    o = _run(env, agent, advs, idx=idx if n_adv > 1 else None, det=True, det_adv=True)
-    with torch.no_grad():
-        x = o['obs'][:K]
-        torch.testing.assert_close(o['act'], agent.ac.actor(x)[0], rtol=1e-4, atol=2e-5)
-        torch.testing.assert_close(o['aact'], adv_mean_logstd(x)[0], rtol=1e-4, atol=2e-5)
-    # stochastic: both log-probabilities are the Gaussian log-prob of the stored action under the PyTorch actor
-    env.reset_tensors()
-    o = _run(env, agent, advs, idx=idx if n_adv > 1 else None)
-    with torch.no_grad():
-        x = o['obs'][:K]
-        mean, logstd = agent.ac.actor(x.reshape(K * N, nobs))
-        lp = normal_log_prob(mean, logstd, o['act'].reshape(K * N, -1)).reshape(K, N)
-        torch.testing.assert_close(o['logp'], lp, rtol=1e-4, atol=1e-4)
-        m, s = adv_mean_logstd(x)
-        lpa = (-0.5 * ((o['aact'] - m) / s.exp()) ** 2 - s - 0.9189385332046727).sum(-1)
-        torch.testing.assert_close(o['alogp'], lpa, rtol=1e-4, atol=1e-4)
-        z = ((o['aact'] - m) / s.exp()).reshape(-1)
-        assert abs(float(z.mean())) < 0.1 and abs(float(z.std()) - 1.0) < 0.1
+    def check(o, start, det, det_adv):          # the protagonist's and each env's own adversary's rows against the float64 actors
+        RN.check_actor('protagonist', agent.ac.actor, o['obs'][:K], o['act'], o['logp'], det, *RN.model_draws(o, start, pm.CH_POLICY, nu, seed=5))
+        e6, r6 = RN.model_draws(o, start, pm.CH_ADVERSARY, ad, seed=5)
+        for j, adv in enumerate(advs):
+            rows = idx == j
+            RN.check_actor(f'adversary {j}', adv, o['obs'][:K][:, sel == j], o['aact'][:, sel == j], o['alogp'][:, sel == j], det_adv,
+                           e6[:, rows], r6[:, rows])
+    # deterministic on both sides: the actors' means on the stored observations; stochastic: both actions are mean + sigma x the host
+    # Philox model's draw (channel 5 / channel 6) at the env's counters, both log-probabilities the float64 Gaussian log-prob; and the
+    # two mixed modes
+    for det, det_adv in ((True, True), (False, False), (False, True), (True, False)):
+        env.reset_tensors()
+        start = env.get_counters() + (np.arange(N),)
+        check(_run(env, agent, advs, idx=idx if n_adv > 1 else None, det=det, det_adv=det_adv), start, det, det_adv)
     env.close()
 
 
@@ -197,11 +187,12 @@ def test_rap_env_results_do_not_depend_on_its_wave_mates():
 
 def test_adversary_noise_is_a_separate_stream_from_the_protagonists():
     """Scale = offset = 0: the adversary cannot act, so the protagonist's rows equal scg_rollout_policy's on an identically seeded handle
-    (step 0 bit for bit); the adversary's recovered noise differs from the protagonist's."""
+    (step 0 bit for bit); the adversary's noise is the host Philox model's channel 6, the protagonist's its channel 5."""
     env, ref = _env(G.ADV_ZERO, 1), _env(G.ADV_ZERO, 1)
     agent, advs = _actors(env, 1, seed=5)
     with torch.no_grad():
         advs[0].logstd.copy_(agent.ac.actor.logstd[:env.spec.adversary_dim])
+    start = env.get_counters() + (np.arange(N),)
     o = _run(env, agent, advs)
     nobs, nu = env.spec.obs_dim, env.spec.nu
     f = dict(device=env.device, dtype=torch.float32)
@@ -212,13 +203,12 @@ def test_adversary_noise_is_a_separate_stream_from_the_protagonists():
     assert torch.equal(o['act'][0], act[0]) and torch.equal(o['logp'][0], logp[0]) and torch.equal(o['obs'][0], obs[0])
     torch.testing.assert_close(o['act'], act, rtol=2e-4, atol=2e-5)
     torch.testing.assert_close(o['rew'], rew, rtol=2e-4, atol=2e-5)
-    with torch.no_grad():
-        x = o['obs'][:K]
-        mean, ls = agent.ac.actor(x)
-        amean, als = advs[0](x)
-        ep = (o['act'] - mean) / ls.exp()
-        ea = (o['aact'] - amean) / als.exp()
-    assert float((ep[..., :ea.shape[-1]] - ea).abs().mean()) > 0.5
+    # the protagonist's noise is the host model's channel 5, the adversary's its channel 6, at the same counters
+    from tests import philox_model as pm
+    from tests import test_gpu_rollout_noise as RN
+    RN.check_actor('protagonist', agent.ac.actor, o['obs'][:K], o['act'], o['logp'], False, *RN.model_draws(o, start, pm.CH_POLICY, nu, seed=5))
+    RN.check_actor('adversary', advs[0], o['obs'][:K], o['aact'], o['alogp'], False,
+                   *RN.model_draws(o, start, pm.CH_ADVERSARY, env.spec.adversary_dim, seed=5))
     env.close(); ref.close()
 
 

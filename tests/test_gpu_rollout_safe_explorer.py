@@ -114,24 +114,12 @@ def _reference(actor, layer, obs, c):
 
 
 def _channel5(env, done, k):
-    """The kernel's channel-5 N(0, 1) draws (scg_rollout_policy's) per step and env from the host Philox model: counter (env, episode,
-    step in episode, tag(5, 0, 0)); the envs were reset once (episode 0) and auto-reset where done."""
-    from oracle.rng import PhiloxEnvRng, make_tag, u01_from_word
+    """The kernel's channel-5 N(0, 1) draws (scg_rollout_policy's) per step and env from the host Philox model (tests/philox_model.py):
+    counter (env, episode, step in episode, tag(5, 0, 0)); the envs were reset once (episode 0) and auto-reset where done."""
+    from tests import philox_model as pm
     n = env.num_envs
-    rng = PhiloxEnvRng(env.seed_value, np.arange(n))
-    ep, st = np.zeros(n, np.int64), np.zeros(n, np.int64)
-    d = done.cpu().numpy().astype(bool)
-    out = np.zeros((k, n, 4))
-    for t in range(k):
-        w = rng.words(np.arange(n), ep.astype(np.uint32), st.astype(np.uint32), make_tag(5, 0, 0))
-        u = u01_from_word(w)
-        r0, r1 = np.sqrt(-2.0 * np.log(u[:, 0])), np.sqrt(-2.0 * np.log(u[:, 2]))
-        out[t] = np.stack([r0 * np.cos(2 * np.pi * u[:, 1]), r0 * np.sin(2 * np.pi * u[:, 1]), r1 * np.cos(2 * np.pi * u[:, 3]),
-                           r1 * np.sin(2 * np.pi * u[:, 3])], axis=1)
-        st += 1
-        ep[d[t]] += 1
-        st[d[t]] = 0
-    return out
+    ep, st = pm.follow(np.zeros(n, np.int64), np.zeros(n, np.int64), done[:k].cpu().numpy())
+    return pm.env_normal4(env.seed_value, env.env_id_offset + np.arange(n)[None, :], ep, st, pm.CH_POLICY)[0]
 
 
 @pytest.mark.parametrize('epw,wpw', GEOMETRIES)
