@@ -23,7 +23,8 @@ def main():
     ap.add_argument('--seed', type=int, default=42)
     ap.add_argument('--checkpoint', default=None)
     ap.add_argument('--train-steps', type=int, default=20000)
-    ap.add_argument('--hidden', type=int, default=64, help='32, 64, 96 or 128; 256 keeps the eager evaluation loop, and the filtered leg is skipped: the filter runs only fused')
+    ap.add_argument('--hidden', type=int, default=64, help='32, 64, 96, 128 or 256; 256 (upstream\'s default width) implies the controller key wide_actor=True: the agent trains in PyTorch, both '
+                         'evaluation legs are still one launch each')
     a = ap.parse_args()
     from safe_control_gym_amd.registration import make
     with open(os.path.join(ROOT, 'tests', 'golden', 'cbf_settings.json')) as f:
@@ -32,8 +33,9 @@ def main():
     cfg.pop('seed', None)
     env_func = partial(make, s['task'], **cfg)
     out = tempfile.mkdtemp()
+    wide = dict(wide_actor=True) if a.hidden == 256 else {}
     ctrl = make('sac', env_func, training=True, output_dir=out, checkpoint_path=os.path.join(out, 'model_latest.pt'), seed=a.seed,
-                hidden_dim=a.hidden, activation='leaky_relu', fused_rollout=True, max_env_steps=a.train_steps, warm_up_steps=min(1000, a.train_steps // 2))
+                hidden_dim=a.hidden, activation='leaky_relu', fused_rollout=True, max_env_steps=a.train_steps, warm_up_steps=min(1000, a.train_steps // 2), **wide)
     if a.checkpoint:
         ctrl.load(a.checkpoint)
     else:

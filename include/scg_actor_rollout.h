@@ -12,6 +12,14 @@
  * (scg_cbf.h) export it too; one built without a kind returns SCG_ERR_INVALID (scg_last_error says why) and launches nothing.  The
  * simulator's own libraries (libscg_hip.so, libscg_spec_<hash>[_pol<H>_<act>].so) are unchanged and do not carry the symbols.
  * Sampled actions (SAC) and exploration noise (DDPG) are not part of it: scg_sac_sample / scg_ddpg_noisy_act keep those.
+ *
+ * Hidden widths: 32 / 64 / 96 / 128 in the libraries above, and 256 in libscg_spec_<hash>_wide256_<act>_<sac|ddpg>.so
+ * (safe_control_gym_amd/csrc/scg_actor_rollout_wide.hip, built with -DSCG_ACTOR_WIDE_H=256 -DSCG_ACTOR_WIDE_ACT= -DSCG_ACTOR_WIDE_KIND= and
+ * without -DSCG_POLICY_H=) and libscg_cbfroll_<hash>_256_<act>_<sac|ddpg>.so (csrc/scg_cbf_wide.hip): the same entry points, structs and
+ * argument checks, scg_actor_rollout_shape reports 256.  There the second layer's weights live in registers, split by output rows over
+ * the 8 waves of a workgroup (csrc/scg_mlp_rows.h); a workgroup serves 1 or 8 tiles of 32 envs (chosen by num_envs,
+ * SCG_ROLLOUT_WIDE_TILES=1|8 overrides it for measurements; results do not depend on it; SCG_ROLLOUT_EPW / SCG_ROLLOUT_WPW are not
+ * read).  A 256 library exports scg_rollout_policy like every library and refuses there: PPO's rollout has no width 256.
  */
 #ifndef SCG_ACTOR_ROLLOUT_H
 #define SCG_ACTOR_ROLLOUT_H

@@ -2,7 +2,8 @@
 batched certify kernel and as the policy rollout with the filter between the actor and the env step, compiled per task config and
 actor shape from csrc/scg_cbf.hip.  The filter's own settings travel by value (CbfParams): one library serves every filter config.
 The library carries every scg_hip.h entry point as well (_lib.EXPORTS): HipVecEnv(..., policy=(hidden, activation), cbf=True) drives
-its handle with it.  No fallback lives here: a shape or a system the library does not serve is an error."""
+its handle with it.  With a kind and hidden width 256 the library is built from csrc/scg_cbf_wide.hip instead (same name pattern, its
+own source hash: source_hash(wide=True)) and serves scg_rollout_cbf_actor and scg_cbf_certify; scg_rollout_cbf refuses there.  No fallback lives here: a shape or a system the library does not serve is an error."""
 import ctypes as C
 import os
 import subprocess
@@ -17,6 +18,14 @@ DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversar
                                                                          os.path.join(L.CSRC_DIR, 'scg_cbf_actor.h')] + \
     [os.path.normpath(os.path.join(L.CSRC_DIR, d)) for d in L.ACTOR_DEPS[1:]]
 PREFIX = 'libscg_cbfroll_'
+# the filter behind an actor of hidden width 256 (kind given): its own translation unit on csrc/scg_actor_rollout_wide.h
+WIDE_SRC = os.path.join(L.CSRC_DIR, 'scg_cbf_wide.hip')
+WIDE_DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, WIDE_SRC, HEADER] + \
+    [os.path.normpath(os.path.join(L.CSRC_DIR, d)) for d in L.WIDE_DEPS[1:]]
+
+
+def is_wide(hidden, kind):
+    return kind is not None and int(hidden) == L.WIDE_HIDDEN
 
 
 class CbfParams(C.Structure):
@@ -36,10 +45,16 @@ def supported_actor(env_id, obs_dim, hidden, act_dim, activation, kind):
         L.policy_supported(obs_dim, hidden, act_dim, activation)
 
 
-def source_hash():
+def supported_wide_actor(env_id, obs_dim, hidden, act_dim, activation, kind):
+    """The same at hidden width 256 (csrc/scg_cbf_wide.hip on scg_actor_rollout_wide.h): a kind is required, PPO's actor has no such variant."""
+    return kind in L.ACTOR_KINDS and env_id == 'cartpole' and act_dim == 1 and obs_dim in (4, 8) and int(hidden) == L.WIDE_HIDDEN and \
+        L.actor_supported(obs_dim, hidden, act_dim, activation)
+
+
+def source_hash(wide=False):
     import hashlib
     h = hashlib.sha256()
-    for p in DEPS:
+    for p in WIDE_DEPS if wide else DEPS:
         with open(p, 'rb') as f:
             h.update(os.path.basename(p).encode() + b'\0' + f.read())
     return int.from_bytes(h.digest()[:8], 'little')
@@ -59,18 +74,24 @@ def build(cfg, hidden, activation, kind=None, force=False):
     src, h = L.spec_source(cfg)
     hdr, _ = L.spec_paths(h)
     so = lib_path(h, hidden, activation, kind)
-    if not force and os.path.exists(so) and L._lib_source_hash(so) == source_hash():
+    wide = is_wide(hidden, kind)
+    if not force and os.path.exists(so) and L._lib_source_hash(so) == source_hash(wide):
         return so
     os.makedirs(L.SPEC_DIR, exist_ok=True)
     with open(hdr, 'w') as f:
         f.write(src)
     cmd = [L._hipcc(), '--offload-arch=gfx950', '-O3', '-ffp-contract=on', '-std=c++17', '-fPIC', '-shared', '-DSCG_SPEC', '-include', hdr,
-           f'-DSCG_POLICY_H={int(hidden)}', f'-DSCG_POLICY_ACT={L.POLICY_ACTS[activation]}', f'-DSCG_SRC_HASH=0x{source_hash():016x}ULL', '-o', so]
-    if kind is not None:
-        cmd.append(f'-DSCG_POLICY_KIND={L.ACTOR_KINDS[kind]}')
+           f'-DSCG_SRC_HASH=0x{source_hash(wide):016x}ULL', '-o', so]
+    if wide:
+        cmd += [f'-DSCG_ACTOR_WIDE_H={L.WIDE_HIDDEN}', f'-DSCG_ACTOR_WIDE_ACT={L.POLICY_ACTS[activation]}',
+                f'-DSCG_ACTOR_WIDE_KIND={L.ACTOR_KINDS[kind]}']
+    else:
+        cmd += [f'-DSCG_POLICY_H={int(hidden)}', f'-DSCG_POLICY_ACT={L.POLICY_ACTS[activation]}']
+        if kind is not None:
+            cmd.append(f'-DSCG_POLICY_KIND={L.ACTOR_KINDS[kind]}')
     res = None
     for extra in L.sched_flags(cfg):
-        res = subprocess.run(cmd + extra + [SRC], capture_output=True, text=True)
+        res = subprocess.run(cmd + extra + [WIDE_SRC if wide else SRC], capture_output=True, text=True)
         if res.returncode == 0:
             return so
     raise L.ScgError('hipcc failed (CBF rollout build):\n' + res.stdout + res.stderr)
@@ -100,7 +121,7 @@ def lib_for(cfg, hidden, activation, kind=None):
     if key in _libs:
         return _libs[key]
     so = lib_path(*key)
-    if not os.path.exists(so) or L._lib_source_hash(so) != source_hash():
+    if not os.path.exists(so) or L._lib_source_hash(so) != source_hash(is_wide(hidden, kind)):
         if not os.path.exists(L._hipcc()):
             raise L.ScgError(f'{so} is missing or stale and hipcc is not available to build it')
         build(cfg, hidden, activation, kind, force=True)

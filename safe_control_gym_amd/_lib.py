@@ -17,6 +17,10 @@ HEADERS = ['scg_env_core.h', 'scg_env_kernels.h', 'scg_gae_kernels.h', 'scg_mlp.
 # the SAC / DDPG actor rollout's translation unit (policy=(hidden, activation, kind) variants): scg_kernels.hip included whole + these
 ACTOR_SOURCE = 'scg_actor_rollout.hip'
 ACTOR_DEPS = [ACTOR_SOURCE, 'scg_actor_rollout.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')]
+# the same rollout at hidden width 256 (policy=(256, activation, kind)): layer 2 in registers, a translation unit and a build macro of its own
+WIDE_HIDDEN = 256
+WIDE_SOURCE = 'scg_actor_rollout_wide.hip'
+WIDE_DEPS = [WIDE_SOURCE, 'scg_actor_rollout_wide.h', 'scg_mlp_rows.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')]
 SPEC_DIR = os.path.join(PKG_DIR, 'spec')
 
 SCG_ABI_VERSION = 1
@@ -158,7 +162,24 @@ def actor_source_hash():
     return int.from_bytes(h.digest()[:8], 'little')
 
 
+def wide_source_hash():
+    """source_hash() of the width-256 actor-rollout variants: the env library's inputs and the files of WIDE_DEPS."""
+    import hashlib
+    h = hashlib.sha256(source_hash().to_bytes(8, 'little'))
+    for name in WIDE_DEPS:
+        with open(os.path.normpath(os.path.join(CSRC_DIR, name)), 'rb') as f:
+            h.update(os.path.basename(name).encode() + b'\0' + f.read())
+    return int.from_bytes(h.digest()[:8], 'little')
+
+
+def is_wide(policy):
+    """Whether a policy= tuple names the width-256 actor rollout (three elements only: PPO's two-element tuple has no such variant)."""
+    return bool(policy) and len(policy) == 3 and int(policy[0]) == WIDE_HIDDEN
+
+
 def _policy_hash(policy):
+    if is_wide(policy):
+        return wide_source_hash()
     return actor_source_hash() if policy and len(policy) == 3 else source_hash()
 
 
@@ -295,14 +316,17 @@ def policy_tuple(policy):
 def spec_paths(hash_value, policy=None):
     """(header, library) of a specialisation.  policy=(hidden, activation): the variant that also carries the fused
     policy-in-the-loop rollout kernel (scg_rollout_policy) for that actor shape; policy=(hidden, activation, 'sac' | 'ddpg'): the one
-    that carries scg_rollout_actor for that actor as well.  Development variants: SCG_SPEC_TAG=<name>
+    that carries scg_rollout_actor for that actor as well (hidden 256: libscg_spec_<hash>_wide256_<act>_<kind>.so, the translation
+    unit of csrc/scg_actor_rollout_wide.hip — a name no _pol... variant has).  Development variants: SCG_SPEC_TAG=<name>
     selects / builds libscg_spec_<hash>_<name>.so (compiled with the extra flags in SCG_SPEC_FLAGS)."""
     tag = f'{hash_value:016x}'
     var = os.environ.get('SCG_SPEC_TAG', '')
     if policy and len(policy) != 2:
         policy_tuple(policy)
     pol = f'_pol{policy[0]}_{policy[1]}' if policy else ''
-    if policy and len(policy) == 3:
+    if is_wide(policy):                                     # (a name no _pol... variant has: another translation unit, another hash)
+        pol = f'_wide{WIDE_HIDDEN}_{policy[1]}_{policy[2]}'
+    elif policy and len(policy) == 3:
         pol += f'_{policy[2]}'
     return (os.path.join(SPEC_DIR, f'scg_spec_{tag}.h'),
             os.path.join(SPEC_DIR, f'libscg_spec_{tag}{pol}{"_" + var if var else ""}.so'))
@@ -310,6 +334,13 @@ def spec_paths(hash_value, policy=None):
 
 def policy_supported(obs_dim, hidden, act_dim, activation):
     return 1 <= obs_dim <= 32 and hidden in (32, 64, 96, 128) and 1 <= act_dim <= 4 and activation in POLICY_ACTS
+
+
+def actor_supported(obs_dim, hidden, act_dim, activation):
+    """Shapes scg_rollout_actor serves (the three-element policy= tuples): policy_supported's, and hidden width 256 with the same
+    observation / action / activation limits (csrc/scg_actor_rollout_wide.h)."""
+    return policy_supported(obs_dim, hidden, act_dim, activation) or \
+        (hidden == WIDE_HIDDEN and 1 <= obs_dim <= 32 and 1 <= act_dim <= 4 and activation in POLICY_ACTS)
 
 
 def sched_flags(cfg):
@@ -343,7 +374,7 @@ def build_spec(cfg, force=False, verbose=False, policy=None):
     hdr, so = spec_paths(h, policy)
     os.makedirs(SPEC_DIR, exist_ok=True)
     kind = bool(policy) and len(policy) == 3
-    srcs = [os.path.join(CSRC_DIR, s) for s in ([ACTOR_SOURCE] if kind else SOURCES)]
+    srcs = [os.path.join(CSRC_DIR, s) for s in ([WIDE_SOURCE] if is_wide(policy) else [ACTOR_SOURCE] if kind else SOURCES)]
     if not force and os.path.exists(so) and _lib_source_hash(so) == _policy_hash(policy):
         return so
     with open(hdr, 'w') as f:
@@ -351,7 +382,10 @@ def build_spec(cfg, force=False, verbose=False, policy=None):
     hipcc = _hipcc()
     cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-ffp-contract=on', '-std=c++17', '-fPIC', '-shared', '-DSCG_SPEC', '-include', hdr,
            f'-DSCG_SRC_HASH=0x{_policy_hash(policy):016x}ULL', '-o', so] + os.environ.get('SCG_SPEC_FLAGS', '').split()
-    if policy:
+    if is_wide(policy):
+        cmd += [f'-DSCG_ACTOR_WIDE_H={WIDE_HIDDEN}', f'-DSCG_ACTOR_WIDE_ACT={POLICY_ACTS[policy[1]]}',
+                f'-DSCG_ACTOR_WIDE_KIND={ACTOR_KINDS[policy[2]]}']
+    elif policy:
         cmd += [f'-DSCG_POLICY_H={int(policy[0])}', f'-DSCG_POLICY_ACT={POLICY_ACTS[policy[1]]}']
         if len(policy) == 3:
             cmd.append(f'-DSCG_POLICY_KIND={ACTOR_KINDS[policy[2]]}')

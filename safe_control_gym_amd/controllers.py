@@ -270,36 +270,60 @@ class RAP(RARL):
         return rarl.RAP(self.env, pcfg, seed=self.seed, num_adversaries=self.num_adversaries)
 
 
+def offpolicy_fused_shape(spec, algo_config, kind):
+    """Whether a SAC / DDPG controller's evaluation is served by the fused actor rollout: (policy= tuple or None, warning text or None),
+    a function of the task's EnvSpec (obs_dim, nx, nu) and the algo config alone, so it can be asked without a GPU.
+      no `fused_rollout`                       (None, None); `wide_actor=True` without it raises ValueError
+      widths 32 / 64 / 96 / 128                served on the agent's fused path (its flat parameter vector), as ever; `wide_actor` changes nothing
+      width 256                                served with `wide_actor=True` (csrc/scg_actor_rollout_wide.h), from FlatAgent.packed_actor():
+                                               the agent's fused update is not required; without the key it warns, as ever
+      running normalisers, multi-row obs       warn and keep the eager loop, with or without `wide_actor`"""
+    from safe_control_gym_amd import _ddpg, _sac
+    if algo_config.get('wide_actor') and not algo_config.get('fused_rollout'):
+        raise ValueError(f'{kind}: wide_actor=True extends fused_rollout=True (the fused evaluation at hidden_dim 256) and needs that key')
+    if not algo_config.get('fused_rollout'):
+        return None, None
+    hidden, act = algo_config['hidden_dim'], algo_config.get('activation', 'relu')
+    normalised = bool(algo_config.get('norm_obs') or algo_config.get('norm_reward'))
+    single_row = spec.obs_dim in (spec.nx, 2 * spec.nx)
+    if algo_config.get('wide_actor') and hidden == L.WIDE_HIDDEN:
+        ok = L.actor_supported(spec.obs_dim, hidden, spec.nu, act) and single_row and not normalised
+    else:
+        agent_fused = (_sac if kind == 'sac' else _ddpg).supported(spec.obs_dim, hidden, spec.nu, act) \
+            and bool(algo_config.get('cuda_graphs', True)) and bool(algo_config.get('fused_update', True))
+        ok = L.policy_supported(spec.obs_dim, hidden, spec.nu, act) and single_row and agent_fused and not normalised
+    if ok:
+        return (int(hidden), act, kind), None
+    served = 'widths 32, 64, 96, 128 on the fused agent, 256 from the packed actor' if algo_config.get('wide_actor') \
+        else 'widths 32, 64, 96, 128 on the fused agent'                                        # (without the key: the text as ever)
+    return None, (f'{kind}: fused_rollout=True is not served for hidden_dim {hidden} / {act} / obs {spec.obs_dim} '
+                  f'({served}, no running normaliser): keeping the eager evaluation loop')
+
+
 class _OffPolicy(HipController):
     """What SAC and DDPG share.  Extension key `fused_rollout=True` (not in SAC_DEFAULTS / DDPG_DEFAULTS, which equal the YAML files):
     the envs are built with the actor's shape and kind (HipVecEnv(..., policy=(hidden_dim, activation, 'sac' | 'ddpg'))), so that run()
     and the evaluations inside learn() are ONE scg_rollout_actor launch, and run(safety_filter=) one scg_rollout_cbf_actor launch.  A
     shape the kernel does not serve (hidden_dim 256, the YAML default), an agent off its fused path or a running normaliser warns once
-    and keeps the eager evaluation loop.  Training collection is unchanged either way."""
+    and keeps the eager evaluation loop.  Training collection is unchanged either way.
+    Extension key `wide_actor=True` (not a default either; needs `fused_rollout=True`, ValueError otherwise): hidden_dim 256 joins the
+    served widths.  The agent stays off its fused path at that width (training collection and gradient steps in PyTorch); the rollout
+    reads FlatAgent.packed_actor(), refreshed from the module's parameters before every launch.  offpolicy_fused_shape decides."""
     KIND = None
 
     def _policy_shape(self):
-        if not self.algo_config.get('fused_rollout'):
-            return None
         if not hasattr(self, '_fused_shape'):
-            from safe_control_gym_amd import _ddpg, _sac
             from safe_control_gym_amd.env_config import EnvSpec
-            spec = EnvSpec(self.env_id, dict(self.task_config))
-            act = self.algo_config.get('activation', 'relu')
-            extra = self.algo_config
-            agent_fused = (_sac if self.KIND == 'sac' else _ddpg).supported(spec.obs_dim, self.hidden_dim, spec.nu, act) \
-                and bool(extra.get('cuda_graphs', True)) and bool(extra.get('fused_update', True))
-            ok = L.policy_supported(spec.obs_dim, self.hidden_dim, spec.nu, act) and spec.obs_dim in (spec.nx, 2 * spec.nx) \
-                and agent_fused and not (self.norm_obs or self.norm_reward)
-            if not ok:
+            cfg = dict(self.algo_config, hidden_dim=self.hidden_dim, norm_obs=self.norm_obs, norm_reward=self.norm_reward)
+            self._fused_shape, warning = offpolicy_fused_shape(EnvSpec(self.env_id, dict(self.task_config)), cfg, self.KIND)
+            if warning:
                 import warnings
-                warnings.warn(f'{self.KIND}: fused_rollout=True is not served for hidden_dim {self.hidden_dim} / {act} / obs {spec.obs_dim} '
-                              f'(widths 32, 64, 96, 128 on the fused agent, no running normaliser): keeping the eager evaluation loop')
-            self._fused_shape = (int(self.hidden_dim), act, self.KIND) if ok else None
+                warnings.warn(warning)
         return self._fused_shape
 
     def _mark_fused(self):
-        self.impl._fused_rollout = bool(self._policy_shape() is not None and self.impl.agent.use_fused)
+        wide = self._policy_shape() is not None and self._policy_shape()[0] == L.WIDE_HIDDEN       # (served from the packed copy)
+        self.impl._fused_rollout = bool(self._policy_shape() is not None and (self.impl.agent.use_fused or wide))
         if self._policy_shape() is not None and not self.impl._fused_rollout:       # (e.g. several ranks: the agent left its fused path)
             import warnings
             warnings.warn(f'{self.KIND}: fused_rollout=True, but the agent is not on its fused path (no flat parameter vector): keeping the '

@@ -167,13 +167,50 @@ class FlatAgent:
             fl['_act_bounds'] = ((C.c_float * 4)(*(fl['low'] + pad)), (C.c_float * 4)(*(fl['high'] + pad)))
         return fl['_act_bounds']
 
+    def packed_actor(self):
+        """The actor's six tensors as ONE packed float32 vector, for agents off the fused path (no flat parameter vector), laid out as
+        the fused agent's actor block: W1, b1, W2, b2, W3, b3 in nn.Linear layout, SAC's W3 / b3 the stacked [2 act_dim][H] head whose
+        first act_dim rows are the mean's.  A persistent buffer on the parameters' device (its pointer never changes), refreshed in
+        place from the module's parameters on every call.  Returns {'p': the vector, 'offsets': {'W1': ..., ..., 'b3': ...} in floats,
+        'low' / 'high': the float[4] bounds}."""
+        a = self.ac.actor
+        fcs = a.net.fcs
+        if hasattr(a, 'mu_layer'):                  # SAC: trunk of two layers, the two heads stacked (mean rows first)
+            parts = {'W1': [fcs[0].weight], 'b1': [fcs[0].bias], 'W2': [fcs[1].weight], 'b2': [fcs[1].bias],
+                     'W3': [a.mu_layer.weight, a.log_std_layer.weight], 'b3': [a.mu_layer.bias, a.log_std_layer.bias]}
+        else:                                       # DDPG: the output layer is the third of the trunk
+            parts = {n + str(k + 1): [getattr(fcs[k], attr)] for k in range(3) for n, attr in (('W', 'weight'), ('b', 'bias'))}
+        order = ('W1', 'b1', 'W2', 'b2', 'W3', 'b3')
+        pk = getattr(self, '_packed_actor', None)
+        if pk is None:
+            if len(fcs) != (2 if hasattr(a, 'mu_layer') else 3):
+                raise ValueError('the packed actor vector serves two hidden layers')
+            offsets, off = {}, 0
+            for name in order:
+                offsets[name] = off
+                off += sum(t.numel() for t in parts[name])
+            pad = [0.0] * (4 - self.act_dim)
+            low, high = ([float(x) for x in torch.as_tensor(b).reshape(-1)] for b in (a.low, a.high))
+            pk = self._packed_actor = {'p': torch.empty(off, dtype=torch.float32, device=fcs[0].weight.device), 'offsets': offsets,
+                                       'low': (C.c_float * 4)(*(low + pad)), 'high': (C.c_float * 4)(*(high + pad))}
+        with torch.no_grad():
+            for name in order:
+                off = pk['offsets'][name]
+                for t in parts[name]:
+                    pk['p'][off:off + t.numel()].copy_(t.detach().reshape(-1))
+                    off += t.numel()
+        return pk
+
     def actor_struct(self):
         """The scg_actor (_lib.Actor, include/scg_actor_rollout.h) of the deterministic actor for the fused rollout (HipVecEnv.rollout_actor):
         the flat vector's actor layout (SAC: W3 / b3 the stacked head, whose first act_dim rows are the mean's) and the padded bounds.
-        Fused agents only."""
+        An agent off its fused path (hidden width 256, fused_update off) has no flat vector: the struct then points at packed_actor()'s
+        copy, refreshed by this call."""
         from safe_control_gym_amd import _lib as L
         if not self.use_fused:
-            raise L.ScgError('actor_struct needs the fused agent (the flat parameter vector)')
+            pk = self.packed_actor()
+            return L.Actor(d_params=pk['p'].data_ptr(), **pk['offsets'], hidden=self.cfg.hidden_dim, activation=L.POLICY_ACTS[self.cfg.activation],
+                           kind=L.ACTOR_KINDS[self.ACTOR_KIND], act_low=pk['low'], act_high=pk['high'])
         fl, lay = self._flat, self._flat['actor']
         lo, hi = self.act_bounds()
         return L.Actor(d_params=fl['p'].data_ptr(), W1=lay.W1, b1=lay.b1, W2=lay.W2, b2=lay.b2, W3=lay.W3, b3=lay.b3, hidden=self.cfg.hidden_dim,

@@ -232,7 +232,9 @@ class HipVecEnv(VecEnv):
         self.policy_shape = None
         if policy is not None and len(policy) != 2:
             policy = L.policy_tuple(policy)
-        if policy is not None and dtype == torch.float32 and L.policy_supported(self.spec.obs_dim, int(policy[0]), self.spec.nu, policy[1]) \
+        # (three-element tuples also at hidden width 256, L.actor_supported: the library of csrc/scg_actor_rollout_wide.h)
+        served = L.actor_supported if policy is not None and len(policy) == 3 else L.policy_supported
+        if policy is not None and dtype == torch.float32 and served(self.spec.obs_dim, int(policy[0]), self.spec.nu, policy[1]) \
                 and self.spec.obs_dim in (self.spec.nx, 2 * self.spec.nx):
             self.policy_shape = (int(policy[0]), policy[1]) + tuple(policy[2:])
         self.actor_kind = self.policy_shape[2] if self.policy_shape is not None and len(self.policy_shape) == 3 else None
@@ -273,7 +275,8 @@ class HipVecEnv(VecEnv):
                 raise NotImplementedError('[Error] Currently CBF is only implemented for the cartpole system.')
             served = self.policy_shape is not None and (
                 _cbf.supported(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1]) if self.actor_kind is None
-                else _cbf.supported_actor(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1], self.actor_kind))
+                else _cbf.supported_actor(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1], self.actor_kind)
+                or _cbf.supported_wide_actor(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1], self.actor_kind))
             if not served:
                 raise L.ScgError('cbf=True needs a float32 env and policy=(hidden, activation) of a shape the fused policy rollout serves')
             self.cbf_shape = self.policy_shape
