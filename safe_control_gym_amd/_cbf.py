@@ -15,12 +15,14 @@ SRC = os.path.join(L.CSRC_DIR, 'scg_cbf.hip')
 HEADER = os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', 'scg_cbf.h'))
 # the env library's hash inputs (_lib.SOURCES + _lib.HEADERS), the adversarial header the ABI includes, and the two new files
 DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, SRC, HEADER,
+                                                                         os.path.join(L.CSRC_DIR, 'scg_cbf_core.h'),
                                                                          os.path.join(L.CSRC_DIR, 'scg_cbf_actor.h')] + \
     [os.path.normpath(os.path.join(L.CSRC_DIR, d)) for d in L.ACTOR_DEPS[1:]]
 PREFIX = 'libscg_cbfroll_'
 # the filter behind an actor of hidden width 256 (kind given): its own translation unit on csrc/scg_actor_rollout_wide.h
 WIDE_SRC = os.path.join(L.CSRC_DIR, 'scg_cbf_wide.hip')
-WIDE_DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, WIDE_SRC, HEADER] + \
+WIDE_DEPS = [os.path.join(L.CSRC_DIR, s) for s in L.SOURCES + L.HEADERS] + [_adversarial.HEADER, WIDE_SRC, HEADER,
+                                                                              os.path.join(L.CSRC_DIR, 'scg_cbf_core.h')] + \
     [os.path.normpath(os.path.join(L.CSRC_DIR, d)) for d in L.WIDE_DEPS[1:]]
 
 

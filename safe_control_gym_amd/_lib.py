@@ -12,8 +12,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC_DIR = os.path.join(PKG_DIR, 'csrc')
 LIB_PATH = os.path.join(PKG_DIR, 'libscg_hip.so')
 SOURCES = ['scg_kernels.hip']
-HEADERS = ['scg_env_core.h', 'scg_env_kernels.h', 'scg_gae_kernels.h', 'scg_mlp.h', 'scg_once.h', 'scg_params.h', 'scg_rng.h', 'scg_spec.h',
-           os.path.join('..', '..', 'include', 'scg_hip.h')]         # (scg_mlp.h: the policy-in-the-loop variants include it)
+HEADERS = ['scg_env_core.h', 'scg_env_kernels.h', 'scg_gae_kernels.h', 'scg_mlp.h', 'scg_once.h', 'scg_params.h', 'scg_rng.h',
+           'scg_rollout_common.h', 'scg_spec.h',
+           os.path.join('..', '..', 'include', 'scg_hip.h')]         # (scg_mlp.h, scg_rollout_common.h: the policy-in-the-loop variants include them)
 # the SAC / DDPG actor rollout's translation unit (policy=(hidden, activation, kind) variants): scg_kernels.hip included whole + these
 ACTOR_SOURCE = 'scg_actor_rollout.hip'
 ACTOR_DEPS = [ACTOR_SOURCE, 'scg_actor_rollout.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')]

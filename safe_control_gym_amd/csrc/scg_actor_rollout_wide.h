@@ -4,10 +4,12 @@
 // -DSCG_ACTOR_WIDE_ACT= -DSCG_ACTOR_WIDE_KIND= and WITHOUT -DSCG_POLICY_H=, so scg_kernels.hip compiles as in a plain specialised
 // library: rollout_policy_kernel (whose LDS image cannot be launched at 256) is not instantiated and scg_rollout_policy refuses.
 //
-// rollout_actor_wide_kernel follows rollout_actor_kernel (scg_actor_rollout.h) step for step: the same EnvOps::step, auto-reset,
-// terminal observation, ep_stats and episode_acc, the same obs-row stores, the same head expression and FILTER slot.  Only the forward
-// pass differs.  Geometry: 8 waves per workgroup, G column tiles; wave w < G steps the 32 envs of tile w in rollout_actor_kernel's
-// EPW = 32 lane mapping (both lane halves hold env c, half 0 stores), all 8 waves take part in every tile's forward pass.  The waves
+// rollout_actor_wide_kernel is rollout_actor_kernel's loop (scg_actor_rollout.h) with another forward pass and the stepper-wave
+// geometry; the head expression and the FILTER slot are the narrow kernel's.  It keeps its own text for the entry, the block after
+// the env step and the tail (inside `if (stepper)` the shared pieces of scg_rollout_common.h cost some instantiations 2 registers);
+// the no-filter functor, the argument checks and PolicyArgs-free host helpers are the shared ones.
+// Geometry: 8 waves per workgroup, G column tiles; wave w < G steps the 32 envs of tile w in the EPW = 32 lane mapping (both lane
+// halves hold env c, half 0 stores), all 8 waves take part in every tile's forward pass.  The waves
 // w >= G (G = 1: seven of eight) hold their rows of W2 and otherwise only run the forward pass.  A surplus tile (a ragged last
 // workgroup) shadows the last env, takes part in barriers and MFMAs and stores nothing; every barrier is reached by all 512 threads
 // on every step (k_steps is a kernel argument).  Since no wave holds 64 envs, obs rows never leave through the LDS transpose: there
@@ -16,6 +18,7 @@
 
 #include "../../include/scg_actor_rollout.h"
 #include "scg_mlp_rows.h"
+#include "scg_rollout_common.h"
 
 #if defined(SCG_SPEC) && defined(SCG_ACTOR_WIDE_H)
 #if defined(SCG_POLICY_H)
@@ -41,15 +44,6 @@ struct WideActorArgs {
     float* obs; float* act; float* reward; uint8_t* done; uint8_t* flags; float* terminal_obs;
     float* ep_stats; float* episode_acc; int32_t max_episodes;
     float low[4], high[4];
-};
-
-// The action the env step receives is the actor's own; nothing is recorded.
-struct WideNoFilter {
-    template <int NU>
-    __device__ __forceinline__ void operator()(const float*, const float* act, float* applied, size_t, bool) const {
-#pragma unroll
-        for (int a = 0; a < NU; ++a) applied[a] = act[a];
-    }
 };
 
 template <int SYS, bool DIST, int G, int KIND, typename FILTER>
@@ -152,25 +146,6 @@ __global__ __launch_bounds__(64 * MLP_ROWS_WAVES) void rollout_actor_wide_kernel
 
 }  // namespace scg
 
-// Argument checks shared by scg_rollout_actor and scg_rollout_cbf_actor (scg_actor_rollout.h's, against the wide shape); nothing is
-// launched when one fails.
-static int actor_rollout_wide_check(const char* who, const scg_env* env, const scg_actor* actor, int k_steps, const scg_policy_rollout* out) {
-    const std::string w(who);
-    if (k_steps <= 0) return fail(SCG_ERR_INVALID, "k_steps must be positive");
-    if (!env->has_reset) return fail(SCG_ERR_STATE, "scg_reset (all envs) must be called before " + w);
-    if (actor->hidden != SCG_ACTOR_WIDE_H || actor->activation != SCG_ACTOR_WIDE_ACT || actor->kind != SCG_ACTOR_WIDE_KIND)
-        return fail(SCG_ERR_INVALID, "this library was compiled for another actor shape (hidden / activation / kind)");
-    if (!actor->d_params || !out->d_obs || !out->d_act || !out->d_reward || !out->d_done || !out->d_flags)
-        return fail(SCG_ERR_INVALID, w + " needs d_params, d_obs, d_act, d_reward, d_done and d_flags");
-    if (((uintptr_t)out->d_obs | (uintptr_t)out->d_terminal_obs | (uintptr_t)out->d_ep_stats | (uintptr_t)out->d_episode_acc) & 15)
-        return fail(SCG_ERR_INVALID, "row outputs must be 16-byte aligned");
-    if constexpr ((scg_make_spec_cfg<float>().nobs * sizeof(float)) % 16 == 0) {      // rows leave as 16-byte pieces: obs[t] must stay aligned
-        if (((size_t)env->cfg.num_envs * scg_make_spec_cfg<float>().nobs * sizeof(float)) % 16 != 0)
-            return fail(SCG_ERR_INVALID, "num_envs x obs_dim x 4 must be a multiple of 16 (row alignment of the [t]-stacked obs)");
-    }
-    return SCG_OK;
-}
-
 // Column tiles per workgroup.  G = 1 (32 envs per workgroup, 8 waves on one tile's layer 2) has the shorter step; G = 8 (256 envs per
 // workgroup) the throughput.  Measured on MI355X (profiles/actor_rollout_wide_cost.json): a 250-step evaluation with
 // G = 1 takes 4.1-4.3 ms up to 8 192 envs (256 workgroups, one per CU) and doubles with every further 8 192, with G = 8 a flat 20.0-20.8 ms
@@ -232,8 +207,10 @@ extern "C" int scg_actor_rollout_shape(int32_t* hidden, int32_t* activation, int
 extern "C" int scg_rollout_actor(scg_env* env, const scg_actor* actor, int k_steps, const scg_policy_rollout* out, void* stream) {
     if (!env || !actor || !out) return fail(SCG_ERR_INVALID, "NULL argument to scg_rollout_actor");
 #ifdef SCG_ACTOR_ROLLOUT_WIDE
-    if (const int rc = actor_rollout_wide_check("scg_rollout_actor", env, actor, k_steps, out)) return rc;
-    return launch_rollout_actor_wide(env, actor, k_steps, out, scg::WideNoFilter(), stream);
+    std::string why;
+    if (const int rc = actor_rollout_check(&why, "scg_rollout_actor", env, actor, k_steps, out, SCG_ACTOR_WIDE_H, SCG_ACTOR_WIDE_ACT, SCG_ACTOR_WIDE_KIND))
+        return fail(rc, why);
+    return launch_rollout_actor_wide(env, actor, k_steps, out, scg::ActorNoFilter(), stream);
 #else
     (void)k_steps; (void)stream;
     return fail(SCG_ERR_INVALID, "scg_rollout_actor at width 256 needs a float32 library built with -DSCG_ACTOR_WIDE_H=256 "

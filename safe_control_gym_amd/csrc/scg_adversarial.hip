@@ -3,9 +3,9 @@
 //
 // Built only as   hipcc ... -DSCG_SPEC -include <spec header> -DSCG_POLICY_H=<H> -DSCG_POLICY_ACT=<act> -DSCG_ADV_N=<n> scg_adversarial.hip
 // (safe_control_gym_amd/_adversarial.py).  The simulator's translation unit is included whole, so that this file reaches struct
-// scg_env and the shared device code without any edit to it (the env library's source hash, and with it the committed profiles
-// bench.py quotes, stay as they are); the kernel below follows rollout_policy_kernel (scg_env_kernels.h) step for step and adds
-// the adversary.
+// scg_env and the shared device code without any edit to it; the kernel below is rollout_policy_kernel's loop with the adversary's
+// forward pass, draw and control between the protagonist's action and the env step (scg_rollout_common.h: the forward, the draw and
+// the host side).
 #include "scg_kernels.hip"
 
 #include "../../include/scg_adversarial.h"
@@ -52,43 +52,8 @@ struct AdvShape {
     }
 };
 
-// Box-Muller of one 4-word Philox draw (as the protagonist's channel 5 in rollout_policy_kernel)
-__device__ __forceinline__ void normal4(const U4 w, float* eps) {
-    const float r0 = m_sqrt(-2.0f * m_log(u01<float>(w.x))), u0 = u01<float>(w.y);
-    eps[0] = r0 * cos_2pi(u0);
-    eps[1] = r0 * cos_2pi(u0 < 0.25f ? u0 + 0.75f : u0 - 0.25f);        // sin(2 pi u) = cos(2 pi (u - 1/4))
-    const float r1 = m_sqrt(-2.0f * m_log(u01<float>(w.z))), u1 = u01<float>(w.w);
-    eps[2] = r1 * cos_2pi(u1);
-    eps[3] = r1 * cos_2pi(u1 < 0.25f ? u1 + 0.75f : u1 - 0.25f);
-}
-
-// One actor's means for the lane's env: EPW 32 = one column tile (both lane halves hold env c), EPW 64 = the wave's two tiles.
-template <int NOUT, int EPW>
-__device__ __forceinline__ void actor_means(const float* img, const float* xo, const float* xr, int lane, float* mean) {
-    using S = AdvShape;
-    using L = MlpLds<S::NIN, S::HID, NOUT, 16>;
-    constexpr int L1Q = L::L1Q;
-    const int h = lane >> 5;
-    f32x16 h1[L::NT], h2[L::NT];
-    if constexpr (EPW == 32) {
-        mlp_forward_tile<S::NIN, S::HID, NOUT, S::ACT, 16>(img, xo, h1, h2, mean, lane);
-    } else {
-        float x[L1Q], out[NOUT];
-#pragma unroll
-        for (int q = 0; q < L1Q; ++q) x[q] = h == 0 ? xo[q] : xr[q];                    // column tile 0: envs 0..31 of the wave
-        mlp_forward_tile<S::NIN, S::HID, NOUT, S::ACT, 16>(img, x, h1, h2, out, lane);
-#pragma unroll
-        for (int a = 0; a < NOUT; ++a) mean[a] = out[a];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < L1Q; ++q) x[q] = h == 1 ? xo[q] : xr[q];                    // column tile 1: envs 32..63
-        mlp_forward_tile<S::NIN, S::HID, NOUT, S::ACT, 16>(img, x, h1, h2, out, lane);
-#pragma unroll
-        for (int a = 0; a < NOUT; ++a) mean[a] = h ? out[a] : mean[a];
-    }
-}
-
-// rollout_policy_kernel + the adversary.  Per step: protagonist means and sample (channel 5); for every adversary index present in
+// This kernel keeps its own text (on the shared entry / after_step pieces some of its instantiations took more registers); it shares
+// normal4 and mlp_forward_lanes.  Per step: protagonist means and sample (channel 5); for every adversary index present in
 // the wave (a wave-uniform loop over a ballot) that adversary's MLP on the wave's column tiles, each lane keeping its own env's
 // result; the adversary's sample (channel 6) and log-probability; set_adversary_control; the env step.
 template <int EPW, int WPW>
@@ -188,7 +153,7 @@ __global__ __launch_bounds__(64 * WPW) void rollout_adversarial_kernel(const Ins
         }
         // ---- protagonist (rollout_policy_kernel's action and log-probability)
         float mean[NU];
-        actor_means<NU, EPW>(lds, xo, xr, lane, mean);
+        mlp_forward_lanes<NIN, HID, NU, S::ACT, S::ACT, EPW>(lds, xo, xr, lane, mean);
         T act[NU];
         float logp = logp_const;
         if (A.deterministic) {
@@ -211,7 +176,7 @@ __global__ __launch_bounds__(64 * WPW) void rollout_adversarial_kernel(const Ins
         for (int k = 0; k < NADV; ++k) {
             if (NADV > 1 && __ballot(my == k) == 0) continue;
             float m[AD];
-            actor_means<AD, EPW>(lds + LP::END + k * LA::END, xo, xr, lane, m);
+            mlp_forward_lanes<NIN, HID, AD, S::ACT, S::ACT, EPW>(lds + LP::END + k * LA::END, xo, xr, lane, m);
 #pragma unroll
             for (int a = 0; a < AD; ++a) amean[a] = my == k ? m[a] : amean[a];
         }
@@ -303,8 +268,7 @@ extern "C" int scg_rollout_adversarial(scg_env* env, const scg_policy* pol, cons
     if (!env->has_reset) return fail(SCG_ERR_STATE, "scg_reset (all envs) must be called before scg_rollout_adversarial");
     if (pol->hidden != S::HID || pol->activation != S::ACT)
         return fail(SCG_ERR_INVALID, "this library was compiled for another policy shape (hidden / activation)");
-    if (!pol->d_params || !out->d_obs || !out->d_act || !out->d_logp || !out->d_reward || !out->d_done || !out->d_flags || !d_adv_act ||
-        !d_adv_logp)
+    if (!pol->d_params || !rollout_outputs_present(out, true) || !d_adv_act || !d_adv_logp)
         return fail(SCG_ERR_INVALID, "scg_rollout_adversarial needs d_params, d_obs, d_act, d_logp, d_reward, d_done, d_flags, d_adv_act "
                                      "and d_adv_logp");
     for (int k = 0; k < n_adversaries; ++k) {
@@ -312,54 +276,28 @@ extern "C" int scg_rollout_adversarial(scg_env* env, const scg_policy* pol, cons
         if (!a.W1 || !a.b1 || !a.W2 || !a.b2 || !a.W3 || !a.b3 || !a.logstd)
             return fail(SCG_ERR_INVALID, "adversary " + std::to_string(k) + " has a NULL parameter pointer");
     }
-    if (((uintptr_t)out->d_obs | (uintptr_t)out->d_terminal_obs | (uintptr_t)out->d_ep_stats | (uintptr_t)out->d_episode_acc) & 15)
-        return fail(SCG_ERR_INVALID, "row outputs must be 16-byte aligned");
-    if constexpr (S::XPOSE) {      // rows leave as 16-byte pieces: obs[t] must stay aligned
-        if (((size_t)env->cfg.num_envs * S::NIN * sizeof(float)) % 16 != 0)
-            return fail(SCG_ERR_INVALID, "num_envs x obs_dim x 4 must be a multiple of 16 (row alignment of the [t]-stacked obs)");
-    }
-    // launch geometry: scg_rollout_policy's rule and overrides; the LDS budget may lower the waves per workgroup
-    int epw = env->cfg.num_envs <= 65536 ? 32 : 64;
-    int wpw = env->cfg.num_envs <= 32768 ? 4 : 8;
-    if (const char* o = getenv("SCG_ROLLOUT_EPW")) { if (atoi(o) == 32 || atoi(o) == 64) epw = atoi(o); }
-    if (const char* o = getenv("SCG_ROLLOUT_WPW")) { if (atoi(o) == 4 || atoi(o) == 8) wpw = atoi(o); }
-    wpw = S::wpw_used(wpw);
-    if (wpw == 0)
+    if (!rollout_rows_aligned(out)) return fail(SCG_ERR_INVALID, "row outputs must be 16-byte aligned");
+    if (const char* why = rollout_obs_stack_error(S::XPOSE, env->cfg.num_envs, S::NIN)) return fail(SCG_ERR_INVALID, why);
+    // the LDS budget may lower the waves per workgroup
+    RolloutGeometry g = rollout_geometry(env->cfg.num_envs);
+    g.wpw = S::wpw_used(g.wpw);
+    if (g.wpw == 0)
         return fail(SCG_ERR_INVALID, "the weight images of the protagonist and " + std::to_string(S::N_ADV) + " adversaries need " +
                                          std::to_string(S::bytes(4)) + " B of LDS per workgroup, more than the 163840 B of a CU");
     HIP_TRY(hipSetDevice(env->device));
-    PolicyArgs A;
-    A.params = pol->d_params; A.W1 = pol->W1; A.b1 = pol->b1; A.W2 = pol->W2; A.b2 = pol->b2; A.W3 = pol->W3; A.b3 = pol->b3;
-    A.logstd_off = pol->logstd_off; A.deterministic = pol->deterministic; A.k_steps = k_steps;
-    A.obs = (float*)out->d_obs; A.act = (float*)out->d_act; A.logp = (float*)out->d_logp; A.reward = (float*)out->d_reward;
-    A.done = out->d_done; A.flags = out->d_flags; A.terminal_obs = (float*)out->d_terminal_obs;
-    A.ep_stats = (float*)out->d_ep_stats; A.episode_acc = (float*)out->d_episode_acc; A.max_episodes = out->max_episodes;
+    PolicyArgs A = policy_args(pol, out, k_steps, pol->deterministic);
+    A.logstd_off = pol->logstd_off;
     AdvArgs B;
     for (int k = 0; k < S::N_ADV; ++k)
         B.adv[k] = {advs[k].W1, advs[k].b1, advs[k].W2, advs[k].b2, advs[k].W3, advs[k].b3, advs[k].logstd};
     B.adv_index = d_adv_index; B.deterministic = deterministic_adversary;
     B.scale = (float)env->cfg.adversary_scale; B.offset = (float)env->cfg.adversary_offset;
     B.act = (float*)d_adv_act; B.logp = (float*)d_adv_logp;
-    const InstParams<float> I = inst_of<float>(env);
-    const size_t bytes = (size_t)S::bytes(wpw);
-    static scg::PerDeviceOnce attr;         // (per device, scg_once.h: the caller has made the handle's device current)
-    int attr_dev;
-    if (attr.pending(&attr_dev)) {
-        const int b4 = S::bytes(4), b8 = S::wpw_used(8) == 8 ? S::bytes(8) : b4;
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_adversarial_kernel<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, b4));
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_adversarial_kernel<32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, b4));
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_adversarial_kernel<64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, b8));
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_adversarial_kernel<32, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, b8));
-        attr.commit(attr_dev);
-    }
-    const int per_wg = epw * wpw;
-    const dim3 grid((env->cfg.num_envs + per_wg - 1) / per_wg), block(64 * wpw);
-    hipStream_t st = (hipStream_t)stream;
-    if (epw == 64 && wpw == 4) rollout_adversarial_kernel<64, 4><<<grid, block, bytes, st>>>(I, A, B);
-    else if (epw == 64) rollout_adversarial_kernel<64, 8><<<grid, block, bytes, st>>>(I, A, B);
-    else if (wpw == 4) rollout_adversarial_kernel<32, 4><<<grid, block, bytes, st>>>(I, A, B);
-    else rollout_adversarial_kernel<32, 8><<<grid, block, bytes, st>>>(I, A, B);
-    HIP_TRY(hipGetLastError());
+    static void (*const k[4])(InstParams<float>, PolicyArgs, AdvArgs) = {rollout_adversarial_kernel<64, 4>, rollout_adversarial_kernel<64, 8>,
+                                                                        rollout_adversarial_kernel<32, 4>, rollout_adversarial_kernel<32, 8>};
+    static scg::PerDeviceOnce attr;
+    HIP_TRY(launch_rollout(k, attr, S::bytes(4), S::wpw_used(8) == 8 ? S::bytes(8) : S::bytes(4), g, env->cfg.num_envs, (size_t)S::bytes(g.wpw),
+                           (hipStream_t)stream, inst_of<float>(env), A, B));
     return SCG_OK;
 #else
     (void)d_adv_index; (void)deterministic_adversary; (void)k_steps; (void)d_adv_act; (void)d_adv_logp; (void)stream;

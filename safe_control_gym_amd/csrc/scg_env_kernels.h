@@ -667,6 +667,9 @@ __global__ __launch_bounds__(BLOCK) void step_sequence_kernel(const CfgParams<T>
 }
 
 #if defined(SCG_SPEC) && defined(SCG_POLICY_H)
+}  // namespace scg
+#include "scg_rollout_common.h"                    // (PolicyArgs, RNG_CH_POLICY and the pieces the rollout kernels share; it builds on what is above)
+namespace scg {
 // ---------------------------------------------------------------------------------------------------------------
 // K control steps per launch WITH THE POLICY IN THE LOOP (PPO.train_step's collector, controllers/ppo/ppo.py:266-284, and
 // PPO.run's evaluation loop, :210-257): per step, for the 64 envs of a wave, the actor MLP obs -> H -> H -> act_dim
@@ -679,14 +682,6 @@ __global__ __launch_bounds__(BLOCK) void step_sequence_kernel(const CfgParams<T>
 // specialised config's, the hidden width and activation the policy's.
 // One launch replaces K x (policy forward, sampling, log-prob, scg_step, episode statistics) launches; with 65 536 envs the
 // per-step cost is the actor's ~290 MFMA issues per 32 envs (15 us) + the 2.5 us of in-register simulation.
-struct PolicyArgs {
-    const float* params; int32_t W1, b1, W2, b2, W3, b3, logstd_off; int32_t deterministic;
-    int32_t k_steps;
-    float* obs; float* act; float* logp; float* reward; uint8_t* done; uint8_t* flags; float* terminal_obs;
-    float* ep_stats; float* episode_acc; int32_t max_episodes;
-};
-constexpr uint32_t RNG_CH_POLICY = 5;
-
 // EPW = envs per wave.  64: lane = env, the wave runs the actor on its two 32-env column tiles one after the other.
 // 32 (shards of <= 32 768 envs, where 64 envs per wave would leave SIMDs idle: 16 384 envs = 256 waves on 1024 SIMDs):
 // lane (c, h) of both halves carries env c — the two halves simulate the same env redundantly (those lanes would idle

@@ -799,52 +799,24 @@ extern "C" int scg_rollout_policy(scg_env* env, const scg_policy* pol, int k_ste
     if (!env->has_reset) return fail(SCG_ERR_STATE, "scg_reset (all envs) must be called before scg_rollout_policy");
     if (pol->hidden != SCG_POLICY_H || pol->activation != SCG_POLICY_ACT)
         return fail(SCG_ERR_INVALID, "this library was compiled for another policy shape (hidden / activation)");
-    if (!pol->d_params || !out->d_obs || !out->d_act || !out->d_logp || !out->d_reward || !out->d_done || !out->d_flags)
+    if (!pol->d_params || !rollout_outputs_present(out, true))
         return fail(SCG_ERR_INVALID, "scg_rollout_policy needs d_params, d_obs, d_act, d_logp, d_reward, d_done and d_flags");
-    if (((uintptr_t)out->d_obs | (uintptr_t)out->d_terminal_obs | (uintptr_t)out->d_ep_stats | (uintptr_t)out->d_episode_acc) & 15)
-        return fail(SCG_ERR_INVALID, "row outputs must be 16-byte aligned");
+    if (!rollout_rows_aligned(out)) return fail(SCG_ERR_INVALID, "row outputs must be 16-byte aligned");
     HIP_TRY(hipSetDevice(env->device));
     constexpr int S = SCG_SPEC_SYS;
     constexpr bool DD = SCG_SPEC_DIST != 0;
-    if constexpr ((scg_make_spec_cfg<float>().nobs * sizeof(float)) % 16 == 0) {      // rows leave as 16-byte pieces: obs[t] must stay aligned
-        if (((size_t)env->cfg.num_envs * scg_make_spec_cfg<float>().nobs * sizeof(float)) % 16 != 0)
-            return fail(SCG_ERR_INVALID, "num_envs x obs_dim x 4 must be a multiple of 16 (row alignment of the [t]-stacked obs)");
-    }
-    PolicyArgs A;
-    A.params = pol->d_params; A.W1 = pol->W1; A.b1 = pol->b1; A.W2 = pol->W2; A.b2 = pol->b2; A.W3 = pol->W3; A.b3 = pol->b3;
-    A.logstd_off = pol->logstd_off; A.deterministic = pol->deterministic; A.k_steps = k_steps;
-    A.obs = (float*)out->d_obs; A.act = (float*)out->d_act; A.logp = (float*)out->d_logp; A.reward = (float*)out->d_reward;
-    A.done = out->d_done; A.flags = out->d_flags; A.terminal_obs = (float*)out->d_terminal_obs;
-    A.ep_stats = (float*)out->d_ep_stats; A.episode_acc = (float*)out->d_episode_acc; A.max_episodes = out->max_episodes;
-    const InstParams<float> I = inst_of<float>(env);
     constexpr int nobs = scg_make_spec_cfg<float>().nobs;
-    // Launch geometry (scg_env_kernels.h): envs per wave 32 while that gives at most two waves per SIMD (2 x 4 x 256 CUs), else 64; waves
-    // per workgroup 4 up to one wave per SIMD, 8 above (two waves per SIMD behind one weight image).  SCG_ROLLOUT_EPW = 32 | 64 and
-    // SCG_ROLLOUT_WPW = 4 | 8 override (tests run the geometries on small batches; results do not depend on them: Philox streams
-    // are per env, the MFMA sequence per env is the same).
-    int epw = env->cfg.num_envs <= 65536 ? 32 : 64;
-    int wpw = env->cfg.num_envs <= 32768 ? 4 : 8;
-    if (const char* o = getenv("SCG_ROLLOUT_EPW")) { if (atoi(o) == 32 || atoi(o) == 64) epw = atoi(o); }
-    if (const char* o = getenv("SCG_ROLLOUT_WPW")) { if (atoi(o) == 4 || atoi(o) == 8) wpw = atoi(o); }
-    const size_t bytes = MlpLds<nobs, SCG_POLICY_H, Dims<S>::NU, 16>::END * sizeof(float) + (size_t)wpw * 64 * nobs * sizeof(float);
-    const size_t bytes8 = MlpLds<nobs, SCG_POLICY_H, Dims<S>::NU, 16>::END * sizeof(float) + (size_t)8 * 64 * nobs * sizeof(float);
-    static scg::PerDeviceOnce attr;         // (per device, scg_once.h: the caller has made the handle's device current)
-    int attr_dev;
-    if (attr.pending(&attr_dev)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_policy_kernel<S, DD, 64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes8));
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_policy_kernel<S, DD, 32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes8));
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_policy_kernel<S, DD, 64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes8));
-        HIP_TRY(hipFuncSetAttribute((const void*)rollout_policy_kernel<S, DD, 32, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes8));
-        attr.commit(attr_dev);
-    }
-    const int per_wg = epw * wpw;
-    const dim3 grid((env->cfg.num_envs + per_wg - 1) / per_wg), block(64 * wpw);
-    hipStream_t st = (hipStream_t)stream;
-    if (epw == 64 && wpw == 4) rollout_policy_kernel<S, DD, 64, 4><<<grid, block, bytes, st>>>(I, A);
-    else if (epw == 64) rollout_policy_kernel<S, DD, 64, 8><<<grid, block, bytes, st>>>(I, A);
-    else if (wpw == 4) rollout_policy_kernel<S, DD, 32, 4><<<grid, block, bytes, st>>>(I, A);
-    else rollout_policy_kernel<S, DD, 32, 8><<<grid, block, bytes, st>>>(I, A);
-    HIP_TRY(hipGetLastError());
+    if (const char* why = rollout_obs_stack_error((nobs * sizeof(float)) % 16 == 0, env->cfg.num_envs, nobs)) return fail(SCG_ERR_INVALID, why);
+    PolicyArgs A = policy_args(pol, out, k_steps, pol->deterministic);
+    A.logstd_off = pol->logstd_off;
+    // Launch geometry: rollout_geometry (scg_rollout_common.h).  All four kernels may take the LDS of eight waves.
+    const RolloutGeometry g = rollout_geometry(env->cfg.num_envs);
+    constexpr size_t image = MlpLds<nobs, SCG_POLICY_H, Dims<S>::NU, 16>::END * sizeof(float), scratch = 64 * nobs * sizeof(float);
+    static void (*const k[4])(InstParams<float>, PolicyArgs) = {rollout_policy_kernel<S, DD, 64, 4>, rollout_policy_kernel<S, DD, 64, 8>,
+                                                                rollout_policy_kernel<S, DD, 32, 4>, rollout_policy_kernel<S, DD, 32, 8>};
+    static scg::PerDeviceOnce attr;
+    HIP_TRY(launch_rollout(k, attr, (int)(image + 8 * scratch), (int)(image + 8 * scratch), g, env->cfg.num_envs, image + g.wpw * scratch,
+                           (hipStream_t)stream, inst_of<float>(env), A));
     return SCG_OK;
 #else
     (void)k_steps; (void)stream;

@@ -3,8 +3,8 @@
 //
 // Built only as   hipcc ... -DSCG_SPEC -include <spec header> -DSCG_POLICY_H=<H> -DSCG_POLICY_ACT=<act> -DSCG_SAFE_HC=<Hc> scg_safe_explorer.hip
 // (safe_control_gym_amd/_safe_explorer.py).  As in scg_adversarial.hip the simulator's translation unit is included whole, without
-// any edit to it; the kernel follows rollout_policy_kernel (scg_env_kernels.h) step for step and adds the safety layer between the
-// actor's mean and the sample, and the constraint values of the next state after the env step.
+// any edit to it; the kernel is rollout_policy_kernel's loop with the safety layer between the actor's mean and the sample, and the
+// constraint values of the next state after the env step (scg_rollout_common.h: the forward, the draw and the host side).
 #include "scg_kernels.hip"
 
 #include <cstring>
@@ -54,41 +54,6 @@ struct SafeShape {
         return wpw == 8 && WIDE_OK && bytes(8, in_lds) <= SAFE_LDS_BUDGET ? 8 : bytes(4, in_lds) <= SAFE_LDS_BUDGET ? 4 : 0;
     }
 };
-
-// Box-Muller of one 4-word Philox draw (rollout_policy_kernel's channel 5)
-__device__ __forceinline__ void safe_normal4(const U4 w, float* eps) {
-    const float r0 = m_sqrt(-2.0f * m_log(u01<float>(w.x))), u0 = u01<float>(w.y);
-    eps[0] = r0 * cos_2pi(u0);
-    eps[1] = r0 * cos_2pi(u0 < 0.25f ? u0 + 0.75f : u0 - 0.25f);        // sin(2 pi u) = cos(2 pi (u - 1/4))
-    const float r1 = m_sqrt(-2.0f * m_log(u01<float>(w.z))), u1 = u01<float>(w.w);
-    eps[2] = r1 * cos_2pi(u1);
-    eps[3] = r1 * cos_2pi(u1 < 0.25f ? u1 + 0.75f : u1 - 0.25f);
-}
-
-// The actor's mean for the lane's env: EPW 32 = one column tile (both lane halves hold env c), EPW 64 = the wave's two tiles.
-template <int EPW>
-__device__ __forceinline__ void safe_actor_mean(const float* img, const float* xo, const float* xr, int lane, float* mean) {
-    using S = SafeShape;
-    constexpr int L1Q = S::LP::L1Q;
-    const int h = lane >> 5;
-    f32x16 h1[S::LP::NT], h2[S::LP::NT];
-    if constexpr (EPW == 32) {
-        mlp_forward_tile<S::NIN, S::HID, S::NU, S::ACT, 16>(img, xo, h1, h2, mean, lane);
-    } else {
-        float x[L1Q], out[S::NU];
-#pragma unroll
-        for (int q = 0; q < L1Q; ++q) x[q] = h == 0 ? xo[q] : xr[q];                    // column tile 0: envs 0..31 of the wave
-        mlp_forward_tile<S::NIN, S::HID, S::NU, S::ACT, 16>(img, x, h1, h2, out, lane);
-#pragma unroll
-        for (int a = 0; a < S::NU; ++a) mean[a] = out[a];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < L1Q; ++q) x[q] = h == 1 ? xo[q] : xr[q];                    // column tile 1: envs 32..63
-        mlp_forward_tile<S::NIN, S::HID, S::NU, S::ACT, 16>(img, x, h1, h2, out, lane);
-#pragma unroll
-        for (int a = 0; a < S::NU; ++a) mean[a] = h ? out[a] : mean[a];
-    }
-}
 
 // g = W2 relu(W1 x + b1) + b2 of one constraint block `w` (LDS or global: the same instructions, only the operand source differs)
 // for one 32-sample column tile; x[q] = input row(q, h) of the lane's sample.  Layer 1 on the matrix cores (Y^T = W1 X^T, one 32x32
@@ -179,7 +144,8 @@ __device__ __forceinline__ void safe_project(const float* sw, const float* slack
     for (int a = 0; a < S::NU; ++a) mean[a] = __fsub_rn(mean[a], __fmul_rn(best, bg[a]));
 }
 
-// rollout_policy_kernel + the safety layer and the constraint values.  SAFE_LDS: the packed safety layer is copied into LDS behind the
+// This kernel keeps its own text (on the shared entry / after_step pieces some of its instantiations spilled more); it shares normal4
+// and mlp_forward_lanes.  SAFE_LDS: the packed safety layer is copied into LDS behind the
 // actor image (else every wave reads it from memory).
 template <int EPW, int WPW, bool SAFE_LDS>
 __global__ __launch_bounds__(64 * WPW) void rollout_safe_kernel(const InstParams<float> I, const PolicyArgs A, const SafeArgs B) {
@@ -266,7 +232,7 @@ __global__ __launch_bounds__(64 * WPW) void rollout_safe_kernel(const InstParams
         }
         // ---- actor mean, safety projection, sample (rollout_policy_kernel's draw and log-probability around the filtered mean)
         float mean[NU];
-        safe_actor_mean<EPW>(lds, xo, xr, lane, mean);
+        mlp_forward_lanes<NIN, HID, NU, S::ACT, S::ACT, EPW>(lds, xo, xr, lane, mean);
         __builtin_amdgcn_sched_barrier(0);
         {
             // step t's constraint values, read back where the previous step (or the launch) wrote them: not held in registers across
@@ -282,7 +248,7 @@ __global__ __launch_bounds__(64 * WPW) void rollout_safe_kernel(const InstParams
             for (int a = 0; a < NU; ++a) act[a] = mean[a];
         } else {
             float eps[4];
-            safe_normal4(rng_words(key, e.gid, e.episode, (uint32_t)e.step, rng_tag(RNG_CH_POLICY, 0, 0)), eps);
+            normal4(rng_words(key, e.gid, e.episode, (uint32_t)e.step, rng_tag(RNG_CH_POLICY, 0, 0)), eps);
 #pragma unroll
             for (int a = 0; a < NU; ++a) {
                 act[a] = __builtin_fmaf(sigma[a], eps[a], mean[a]);
@@ -381,70 +347,41 @@ extern "C" int scg_rollout_safe(scg_env* env, const scg_actor_ptrs* actor, const
     if (!env->has_reset) return fail(SCG_ERR_STATE, "scg_reset (all envs) must be called before scg_rollout_safe");
     if (!actor->W1 || !actor->b1 || !actor->W2 || !actor->b2 || !actor->W3 || !actor->b3 || !actor->logstd)
         return fail(SCG_ERR_INVALID, "the actor has a NULL parameter pointer");
-    if (!d_safety || !d_slack || !d_c_rows || !d_c_carry || !out->d_obs || !out->d_act || !out->d_logp || !out->d_reward || !out->d_done ||
-        !out->d_flags)
+    if (!d_safety || !d_slack || !d_c_rows || !d_c_carry || !rollout_outputs_present(out, true))
         return fail(SCG_ERR_INVALID, "scg_rollout_safe needs d_safety, d_slack, d_c_rows, d_c_carry, d_obs, d_act, d_logp, d_reward, d_done "
                                      "and d_flags");
-    if (((uintptr_t)out->d_obs | (uintptr_t)out->d_terminal_obs | (uintptr_t)out->d_ep_stats | (uintptr_t)out->d_episode_acc |
-         (uintptr_t)d_safety | (uintptr_t)d_c_rows | (uintptr_t)d_c_carry) & 15)
+    if (!rollout_rows_aligned(out, (uintptr_t)d_safety | (uintptr_t)d_c_rows | (uintptr_t)d_c_carry))
         return fail(SCG_ERR_INVALID, "row outputs, the packed safety layer and the constraint-value buffers must be 16-byte aligned");
-    if constexpr (S::XPOSE) {      // rows leave as 16-byte pieces: obs[t] must stay aligned
-        if (((size_t)env->cfg.num_envs * S::NIN * sizeof(float)) % 16 != 0)
-            return fail(SCG_ERR_INVALID, "num_envs x obs_dim x 4 must be a multiple of 16 (row alignment of the [t]-stacked obs)");
-    }
-    // launch geometry: scg_rollout_policy's rule and overrides; the LDS budget picks the placement and may lower the waves per workgroup
-    int epw = env->cfg.num_envs <= 65536 ? 32 : 64;
-    int wpw = env->cfg.num_envs <= 32768 ? 4 : 8;
-    if (const char* o = getenv("SCG_ROLLOUT_EPW")) { if (atoi(o) == 32 || atoi(o) == 64) epw = atoi(o); }
-    if (const char* o = getenv("SCG_ROLLOUT_WPW")) { if (atoi(o) == 4 || atoi(o) == 8) wpw = atoi(o); }
+    if (const char* stack = rollout_obs_stack_error(S::XPOSE, env->cfg.num_envs, S::NIN)) return fail(SCG_ERR_INVALID, stack);
+    // the LDS budget picks the placement and may lower the waves per workgroup
+    RolloutGeometry g = rollout_geometry(env->cfg.num_envs);
     bool in_lds = false;
     std::string why;
-    wpw = safe_choose(wpw, &in_lds, &why);
-    if (wpw == 0) return fail(SCG_ERR_INVALID, why);
+    g.wpw = safe_choose(g.wpw, &in_lds, &why);
+    if (g.wpw == 0) return fail(SCG_ERR_INVALID, why);
     HIP_TRY(hipSetDevice(env->device));
-    PolicyArgs A;
-    A.params = nullptr; A.W1 = A.b1 = A.W2 = A.b2 = A.W3 = A.b3 = A.logstd_off = 0;
-    A.deterministic = deterministic ? 1 : 0; A.k_steps = k_steps;
-    A.obs = (float*)out->d_obs; A.act = (float*)out->d_act; A.logp = (float*)out->d_logp; A.reward = (float*)out->d_reward;
-    A.done = out->d_done; A.flags = out->d_flags; A.terminal_obs = (float*)out->d_terminal_obs;
-    A.ep_stats = (float*)out->d_ep_stats; A.episode_acc = (float*)out->d_episode_acc; A.max_episodes = out->max_episodes;
+    const PolicyArgs A = policy_args(out, k_steps, deterministic ? 1 : 0);
     SafeArgs B;
     B.actor = MlpWeights{actor->W1, actor->b1, actor->W2, actor->b2, actor->W3, actor->b3};
     B.logstd = actor->logstd; B.safety = d_safety; B.slack = d_slack; B.c_rows = d_c_rows; B.c_carry = d_c_carry;
-    const InstParams<float> I = inst_of<float>(env);
-    const size_t bytes = (size_t)S::bytes(wpw, in_lds);
-    static scg::PerDeviceOnce attr;         // (per device, scg_once.h: the caller has made the handle's device current)
+    static void (*const kg[4])(InstParams<float>, PolicyArgs, SafeArgs) = {rollout_safe_kernel<64, 4, false>, rollout_safe_kernel<64, 8, false>,
+                                                                         rollout_safe_kernel<32, 4, false>, rollout_safe_kernel<32, 8, false>};
+    static void (*const kl[4])(InstParams<float>, PolicyArgs, SafeArgs) = {rollout_safe_kernel<64, 4, true>, rollout_safe_kernel<64, 8, true>,
+                                                                         rollout_safe_kernel<32, 4, true>, rollout_safe_kernel<32, 8, true>};
+    static scg::PerDeviceOnce attr;         // (both placements' attributes on the first call; a placement that does not fit gets the other's size)
     int attr_dev;
     if (attr.pending(&attr_dev)) {
-        for (int lds_side = 0; lds_side < 2; ++lds_side) {
-            const bool il = lds_side == 1;
+        for (int il = 0; il < 2; ++il) {
             const int b4 = S::bytes(4, il) <= SAFE_LDS_BUDGET ? S::bytes(4, il) : S::bytes(4, false);
             const int b8 = S::wpw_used(8, il) == 8 ? S::bytes(8, il) : b4;
-            const void* k4[2] = {il ? (const void*)rollout_safe_kernel<64, 4, true> : (const void*)rollout_safe_kernel<64, 4, false>,
-                                 il ? (const void*)rollout_safe_kernel<32, 4, true> : (const void*)rollout_safe_kernel<32, 4, false>};
-            const void* k8[2] = {il ? (const void*)rollout_safe_kernel<64, 8, true> : (const void*)rollout_safe_kernel<64, 8, false>,
-                                 il ? (const void*)rollout_safe_kernel<32, 8, true> : (const void*)rollout_safe_kernel<32, 8, false>};
-            for (int j = 0; j < 2; ++j) {
-                HIP_TRY(hipFuncSetAttribute(k4[j], hipFuncAttributeMaxDynamicSharedMemorySize, b4));
-                HIP_TRY(hipFuncSetAttribute(k8[j], hipFuncAttributeMaxDynamicSharedMemorySize, b8));
-            }
+            for (int j = 0; j < 4; ++j)
+                HIP_TRY(hipFuncSetAttribute((const void*)(il ? kl : kg)[j], hipFuncAttributeMaxDynamicSharedMemorySize, j & 1 ? b8 : b4));
         }
         attr.commit(attr_dev);
     }
-    const int per_wg = epw * wpw;
-    const dim3 grid((env->cfg.num_envs + per_wg - 1) / per_wg), block(64 * wpw);
-    hipStream_t st = (hipStream_t)stream;
-    if (in_lds) {
-        if (epw == 64 && wpw == 4) rollout_safe_kernel<64, 4, true><<<grid, block, bytes, st>>>(I, A, B);
-        else if (epw == 64) rollout_safe_kernel<64, 8, true><<<grid, block, bytes, st>>>(I, A, B);
-        else if (wpw == 4) rollout_safe_kernel<32, 4, true><<<grid, block, bytes, st>>>(I, A, B);
-        else rollout_safe_kernel<32, 8, true><<<grid, block, bytes, st>>>(I, A, B);
-    } else {
-        if (epw == 64 && wpw == 4) rollout_safe_kernel<64, 4, false><<<grid, block, bytes, st>>>(I, A, B);
-        else if (epw == 64) rollout_safe_kernel<64, 8, false><<<grid, block, bytes, st>>>(I, A, B);
-        else if (wpw == 4) rollout_safe_kernel<32, 4, false><<<grid, block, bytes, st>>>(I, A, B);
-        else rollout_safe_kernel<32, 8, false><<<grid, block, bytes, st>>>(I, A, B);
-    }
+    const int per_wg = g.epw * g.wpw;
+    (in_lds ? kl : kg)[(g.epw == 64 ? 0 : 2) + (g.wpw == 4 ? 0 : 1)]<<<dim3((env->cfg.num_envs + per_wg - 1) / per_wg), dim3(64 * g.wpw),
+                                                                     (size_t)S::bytes(g.wpw, in_lds), (hipStream_t)stream>>>(inst_of<float>(env), A, B);
     HIP_TRY(hipGetLastError());
     return SCG_OK;
 #else

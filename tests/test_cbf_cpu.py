@@ -148,5 +148,11 @@ def test_header_declares_both_entry_points():
     assert declared == [f[0] for f in _cbf.CbfParams._fields_]
     import ctypes as C
     assert C.sizeof(_cbf.CbfParams) == 14 * 4
-    src = open(os.path.join(ROOT, 'safe_control_gym_amd', 'csrc', 'scg_cbf.hip')).read()
-    assert len(re.findall(r'(?<![a-z_])cbf_certify\(', src)) == 3          # ONE device function: its definition and the two kernels' calls
+    # ONE device function in all of csrc/, in the header both CBF translation units include
+    csrc = os.path.join(ROOT, 'safe_control_gym_amd', 'csrc')
+    defs = [n for n in sorted(os.listdir(csrc)) if n.endswith(('.h', '.hip'))
+            and re.search(r'CbfResult\s+cbf_certify\s*\(', open(os.path.join(csrc, n)).read())]
+    assert defs == ['scg_cbf_core.h']
+    assert len(re.findall(r'CbfResult\s+cbf_certify\s*\(', open(os.path.join(csrc, defs[0])).read())) == 1
+    for unit in ('scg_cbf.hip', 'scg_cbf_wide.hip'):
+        assert '#include "scg_cbf_core.h"' in open(os.path.join(csrc, unit)).read()

@@ -119,8 +119,8 @@ def cos_2pi_f32(u):
 
 
 def normal4_f32(w):
-    """The kernels' Box-Muller text (scg_env_kernels.h rollout_policy_kernel, scg_adversarial.hip normal4, scg_cbf.hip,
-    scg_safe_explorer.hip safe_normal4) in NumPy float32, every operation rounded to float32 (no fused multiply-add)."""
+    """The kernels' Box-Muller text (scg_rollout_common.h normal4, and the same text inline in rollout_policy_kernel, scg_env_kernels.h) in NumPy
+    float32, every operation rounded to float32 (no fused multiply-add)."""
     f = np.float32
     u = ((w >> np.uint32(8)).astype(f) + f(0.5)) * f(1.0 / 16777216.0)
     assert u.dtype == f
