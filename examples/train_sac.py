@@ -4,6 +4,8 @@ inertial properties, white-noise dynamics disturbance and constraint evaluation)
 
     python examples/train_sac.py --envs 4096 --max-seconds 30
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_sac.py     # env shards + RCCL
+    python examples/train_sac.py --task quadrotor_3D_track --envs 4 --train-interval 100 --warm-up-steps 1000 --collect-steps 25
+        # upstream's sac.yaml cadence, collected 25 vector steps per launch (scg_rollout_sac_collect; one rank, other samples than stepwise)
 
 Prints one JSON line per log interval and a summary line (env-steps/s incl. learning, mean return of finished episodes).
 """
@@ -28,6 +30,9 @@ def main():
     ap.add_argument('--lr', type=float, default=3e-4)
     ap.add_argument('--buffer', type=int, default=2_000_000)
     ap.add_argument('--warm-up-steps', type=int, default=65536)
+    ap.add_argument('--train-interval', type=int, default=0, help='env steps between updates (default: one vector step of all ranks)')
+    ap.add_argument('--collect-steps', type=int, default=0,
+                    help='K > 0: the chunked collector, up to K vector steps per launch on the same update schedule (needs --train-interval > envs)')
     ap.add_argument('--max-seconds', type=float, default=30.0)
     ap.add_argument('--max-env-steps', type=float, default=1e8)
     ap.add_argument('--seed', type=int, default=1)
@@ -36,10 +41,11 @@ def main():
     args = ap.parse_args()
     rank, world = parallel.init_distributed()
     env_id, cfg = load_task(args.task)
-    env = HipVecEnv(env_id, args.envs, seed=args.seed, env_id_offset=rank * args.envs, return_numpy=False, **cfg)
+    policy = (args.hidden, 'relu', 'sac') if args.collect_steps else None       # the env library that carries the actor and the collector
+    env = HipVecEnv(env_id, args.envs, seed=args.seed, env_id_offset=rank * args.envs, return_numpy=False, policy=policy, **cfg)
     scfg = SACConfig(hidden_dim=args.hidden, train_batch_size=args.batch, actor_lr=args.lr, critic_lr=args.lr,
-                     warm_up_steps=args.warm_up_steps, train_interval=args.envs * world, max_buffer_size=args.buffer,
-                     extra={'updates_per_step': args.updates_per_step})
+                     warm_up_steps=args.warm_up_steps, train_interval=args.train_interval or args.envs * world, max_buffer_size=args.buffer,
+                     extra={'updates_per_step': args.updates_per_step, 'collect_steps': args.collect_steps})
     sac = SAC(env, scfg, seed=args.seed)
     flat = lambda: torch.cat([p.detach().reshape(-1) for p in sac.agent.ac.parameters()]).cpu()      # noqa: E731
     init_params = flat()
@@ -56,9 +62,10 @@ def main():
             break
         res = sac.train_step()
         it += 1
-        d = env.out.done.to(torch.float32)
-        ep_n += float(d.sum()) if it % 16 == 0 else 0.0                       # sampled: a host sync every 16th step only
-        ep_ret += float((env.out.fin_return * d).sum()) if it % 16 == 0 else 0.0
+        if not sac._collect_k:                                                # (the chunked collector does not write the step outputs)
+            d = env.out.done.to(torch.float32)
+            ep_n += float(d.sum()) if it % 16 == 0 else 0.0                   # sampled: a host sync every 16th step only
+            ep_ret += float((env.out.fin_return * d).sum()) if it % 16 == 0 else 0.0
         if rank == 0 and not args.quiet and time.perf_counter() - last_log > 5.0:
             last_log = time.perf_counter()
             print(json.dumps({'step': sac.total_steps, 'wall_clock': last_log - t0, 'mean_episode_return': ep_ret / max(ep_n, 1.0),

@@ -11,7 +11,8 @@
  * -DSCG_POLICY_H= -DSCG_POLICY_ACT= -DSCG_POLICY_KIND=, float32), which also exports everything of scg_hip.h.  The CBF libraries
  * (scg_cbf.h) export it too; one built without a kind returns SCG_ERR_INVALID (scg_last_error says why) and launches nothing.  The
  * simulator's own libraries (libscg_hip.so, libscg_spec_<hash>[_pol<H>_<act>].so) are unchanged and do not carry the symbols.
- * Sampled actions (SAC) and exploration noise (DDPG) are not part of it: scg_sac_sample / scg_ddpg_noisy_act keep those.
+ * Sampled actions (SAC) and exploration noise (DDPG) are not part of it: scg_sac_sample / scg_ddpg_noisy_act keep those, and SAC's
+ * sampled TRAINING collection is an entry point of its own in the same libraries (scg_rollout_sac_collect, scg_actor_collect.h).
  *
  * Hidden widths: 32 / 64 / 96 / 128 in the libraries above, and 256 in libscg_spec_<hash>_wide256_<act>_<sac|ddpg>.so
  * (safe_control_gym_amd/csrc/scg_actor_rollout_wide.hip, built with -DSCG_ACTOR_WIDE_H=256 -DSCG_ACTOR_WIDE_ACT= -DSCG_ACTOR_WIDE_KIND= and

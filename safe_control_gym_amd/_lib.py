@@ -17,11 +17,13 @@ HEADERS = ['scg_env_core.h', 'scg_env_kernels.h', 'scg_gae_kernels.h', 'scg_mlp.
            os.path.join('..', '..', 'include', 'scg_hip.h')]         # (scg_mlp.h, scg_rollout_common.h: the policy-in-the-loop variants include them)
 # the SAC / DDPG actor rollout's translation unit (policy=(hidden, activation, kind) variants): scg_kernels.hip included whole + these
 ACTOR_SOURCE = 'scg_actor_rollout.hip'
-ACTOR_DEPS = [ACTOR_SOURCE, 'scg_actor_rollout.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')]
+# (scg_actor_collect.h: SAC's training collector, scg_rollout_sac_collect — the kernel in the kind sac variants, a refusal elsewhere)
+COLLECT_DEPS = ['scg_actor_collect.h', os.path.join('..', '..', 'include', 'scg_actor_collect.h')]
+ACTOR_DEPS = [ACTOR_SOURCE, 'scg_actor_rollout.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')] + COLLECT_DEPS
 # the same rollout at hidden width 256 (policy=(256, activation, kind)): layer 2 in registers, a translation unit and a build macro of its own
 WIDE_HIDDEN = 256
 WIDE_SOURCE = 'scg_actor_rollout_wide.hip'
-WIDE_DEPS = [WIDE_SOURCE, 'scg_actor_rollout_wide.h', 'scg_mlp_rows.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')]
+WIDE_DEPS = [WIDE_SOURCE, 'scg_actor_rollout_wide.h', 'scg_mlp_rows.h', os.path.join('..', '..', 'include', 'scg_actor_rollout.h')] + COLLECT_DEPS
 SPEC_DIR = os.path.join(PKG_DIR, 'spec')
 
 SCG_ABI_VERSION = 1
@@ -113,6 +115,15 @@ class Actor(C.Structure):
                [('act_low', C.c_float * MAX_ACTION), ('act_high', C.c_float * MAX_ACTION)]
 
 
+class SacCollect(C.Structure):
+    """scg_sac_collect (include/scg_actor_collect.h): the replay ring, the current-observation batch, the mode and the optional trace of
+    SAC's fused training collection."""
+    _fields_ = [(n, c_vp) for n in ('d_ring_obs', 'd_ring_act', 'd_ring_rew', 'd_ring_next_obs', 'd_ring_mask')] + [('capacity', c_i32)] + \
+               [(n, c_vp) for n in ('d_pos', 'd_size_f', 'd_size_i32', 'd_cur_obs')] + [('uniform', c_i32)] + \
+               [(n, c_vp) for n in ('d_ep_stats', 'd_episode_acc')] + [('max_episodes', c_i32)] + \
+               [(n, c_vp) for n in ('d_obs', 'd_act', 'd_reward', 'd_done', 'd_flags', 'd_terminal_obs')]
+
+
 class Sequence(C.Structure):
     _fields_ = [(n, c_vp) for n in ('d_actions', 'd_adv_actions', 'd_obs', 'd_reward', 'd_done', 'd_flags', 'd_terminal_obs',
                                     'd_mse', 'd_c_values', 'd_ep_stats', 'd_fin_stats', 'd_state', 'd_noisy_action')]
@@ -127,6 +138,7 @@ EXPORTS = ['scg_dims', 'scg_workspace_bytes', 'scg_create', 'scg_destroy', 'scg_
            'scg_set_counters', 'scg_get_counters', 'scg_set_seed', 'scg_set_step_launch', 'scg_set_step_wsback', 'scg_rng_layout_version', 'scg_gae', 'scg_prior_model', 'scg_last_error', 'scg_abi_version',
            'scg_sizeof_config', 'scg_sizeof_step_out', 'scg_spec_source', 'scg_spec_hash', 'scg_source_hash']
 ACTOR_EXPORTS = ['scg_rollout_actor', 'scg_actor_rollout_shape']       # (the kind variants and the CBF libraries only)
+COLLECT_EXPORT = 'scg_rollout_sac_collect'                              # (the same libraries; served by the kind sac variants up to width 128)
 
 
 class ScgError(RuntimeError):
@@ -252,6 +264,8 @@ def _bind(path):
     if all(hasattr(L, name) for name in ACTOR_EXPORTS):
         L.scg_rollout_actor.argtypes = [c_vp, C.POINTER(Actor), C.c_int, C.POINTER(PolicyRollout), c_vp]
         L.scg_actor_rollout_shape.argtypes = [C.POINTER(c_i32)] * 3
+    if hasattr(L, COLLECT_EXPORT):
+        L.scg_rollout_sac_collect.argtypes = [c_vp, C.POINTER(Actor), C.c_int, C.POINTER(SacCollect), c_vp]
     for fn in (L.scg_set_state, L.scg_get_state, L.scg_set_params, L.scg_get_params):
         fn.argtypes = [c_vp, C.POINTER(c_f64), C.c_int, C.c_int, c_vp]
     L.scg_set_counters.argtypes = [c_vp, C.POINTER(c_i32), C.POINTER(C.c_uint32), C.c_int, C.c_int, c_vp]

@@ -308,8 +308,26 @@ class _OffPolicy(HipController):
     and keeps the eager evaluation loop.  Training collection is unchanged either way.
     Extension key `wide_actor=True` (not a default either; needs `fused_rollout=True`, ValueError otherwise): hidden_dim 256 joins the
     served widths.  The agent stays off its fused path at that width (training collection and gradient steps in PyTorch); the rollout
-    reads FlatAgent.packed_actor(), refreshed from the module's parameters before every launch.  offpolicy_fused_shape decides."""
+    reads FlatAgent.packed_actor(), refreshed from the module's parameters before every launch.  offpolicy_fused_shape decides.
+    Extension key `collect_steps=K` (not a default either; `sac` only, needs `fused_rollout=True`, ValueError otherwise): training
+    collection runs up to K vector steps per launch, sampled actor inside the env kernel, transitions written straight into the replay
+    ring (scg_rollout_sac_collect, include/scg_actor_collect.h).  Updates happen exactly where the stepwise trainer's do
+    (offpolicy.chunk_steps); K x envs must fit max_buffer_size (ValueError).  It needs the agent on its fused path, no running
+    normaliser, one rank and hidden_dim <= 128: otherwise it warns once and the stepwise collector stays.  The chunked collector draws
+    its action noise from the envs' own Philox streams (addressed by episode / step, so checkpoints carry it through
+    env_random_state), the stepwise one from the agent's counter stream: at the same seed the two train on DIFFERENT samples, which is
+    why the key is opt-in.  On `ddpg` the key raises ValueError: its exploration noise is one process shared by the envs and continued
+    across them in env order."""
     KIND = None
+
+    def _check_collect_steps(self):
+        if not self.algo_config.get('collect_steps'):
+            return
+        if self.KIND != 'sac':
+            raise ValueError(f'{self.KIND}: collect_steps is not served: the exploration noise is ONE shared noise process continued across '
+                             f'the envs in env order, a dependency across the batch inside every step')
+        if not self.algo_config.get('fused_rollout'):
+            raise ValueError(f'{self.KIND}: collect_steps extends fused_rollout=True (the env library that carries the actor) and needs that key')
 
     def _policy_shape(self):
         if not hasattr(self, '_fused_shape'):
@@ -337,6 +355,7 @@ class SAC(_OffPolicy):
 
     def _build(self):
         from safe_control_gym_amd import sac
+        self._check_collect_steps()
         scfg = sac.SACConfig.from_dict(self.algo_config)
         n = self.rollout_batch_size if self.training else self.eval_batch_size
         self.env = self._vec(n, self.seed, self._policy_shape())
@@ -363,6 +382,7 @@ class DDPG(_OffPolicy):
 
     def _build(self):
         from safe_control_gym_amd import ddpg
+        self._check_collect_steps()
         self.activation = self.algo_config.setdefault('activation', 'relu')        # (ddpg.yaml has no such key: DDPGAgent's default)
         dcfg = ddpg.DDPGConfig.from_dict(self.algo_config)
         n = self.rollout_batch_size if self.training else self.eval_batch_size

@@ -149,3 +149,6 @@ extern "C" int scg_rollout_actor(scg_env* env, const scg_actor* actor, int k_ste
                                  "(float32): build it with _lib.build_spec(cfg, policy=(hidden, activation, 'sac' | 'ddpg'))");
 #endif
 }
+
+// scg_rollout_sac_collect (include/scg_actor_collect.h): SAC's training collection; the kernel only where SCG_ACTOR_COLLECT is defined
+#include "scg_actor_collect.h"

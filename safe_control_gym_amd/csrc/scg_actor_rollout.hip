@@ -6,4 +6,6 @@
 // whole, without any edit to it; the kernel and the entry points are in scg_actor_rollout.h, which scg_cbf.hip includes as well.
 #include "scg_kernels.hip"
 
+// kind sac: + the training collector, K vector steps into the replay ring per launch (scg_actor_collect.h, included by scg_actor_rollout.h)
+#define SCG_ACTOR_COLLECT 1
 #include "scg_actor_rollout.h"

@@ -217,3 +217,6 @@ extern "C" int scg_rollout_actor(scg_env* env, const scg_actor* actor, int k_ste
                                  "(_lib.build_spec(cfg, policy=(256, activation, 'sac' | 'ddpg')))");
 #endif
 }
+
+// scg_rollout_sac_collect (include/scg_actor_collect.h) is exported and refuses: the collector has no width 256
+#include "scg_actor_collect.h"

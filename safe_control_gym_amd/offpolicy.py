@@ -13,11 +13,27 @@ differs from the other one through the class attributes and the small hooks name
 import ctypes as C
 import os
 import time
+import warnings
 from copy import deepcopy
 
 import torch
 
 from safe_control_gym_amd import _shapelib, parallel
+
+
+def chunk_steps(total_steps, since_update, n_envs_times_world, warm_up_steps, train_interval, k_max):
+    """Vector steps of the chunked collector's next launch, so that OffPolicyTrainer.train_step's schedule is the stepwise one whatever
+    k_max is.  The stepwise loop, per vector step: the action is uniform while total_steps < warm_up_steps; then total_steps and
+    since_update grow by n_envs_times_world; then an update of since_update gradient steps is owed if total_steps > warm_up_steps and
+    since_update >= train_interval.  A chunk ends at the earliest of: k_max steps; the last warm-up step (one launch has one mode); the
+    first step after which an update is owed (the update must see exactly the transitions the stepwise trainer's would).  >= 1."""
+    nw = int(n_envs_times_world)
+    k = max(int(k_max), 1)
+    if total_steps < warm_up_steps:                     # steps j = 0 .. with total_steps + j nw < warm_up_steps
+        k = min(k, -(-(warm_up_steps - total_steps) // nw))
+    past_warm_up = max((warm_up_steps - total_steps) // nw + 1, 1)         # first j >= 1 with total_steps + j nw > warm_up_steps
+    interval_full = max(-(-(train_interval - since_update) // nw), 1)      # first j >= 1 with since_update + j nw >= train_interval
+    return max(min(k, max(past_warm_up, interval_full)), 1)
 
 
 class OffPolicyConfig:
@@ -355,8 +371,32 @@ class OffPolicyTrainer:
         if self._fused_collect:
             self._act = torch.zeros(self.N, self.act_dim, device=self.device)
             self._collect_counter = torch.zeros(1, dtype=torch.int32, device=self.device)       # counter word of the action noise
+        self._collect_k = self._chunked_collect_steps()
+        self._chunk = None
+
+    def _chunked_collect_steps(self):
+        """K of the chunked collector (extension key `collect_steps`, controllers.py), or 0: the stepwise collector.  A config error
+        raises; a need that is unmet at run time warns once and keeps the stepwise collector."""
+        k = int(self.cfg.extra.get('collect_steps') or 0)
+        if k <= 0:
+            return 0
+        if not self.CHUNKED_COLLECT:
+            raise ValueError(f'{type(self).__name__}: collect_steps is served for SAC only')
+        if k * self.N > self.cfg.max_buffer_size:
+            raise ValueError(f'collect_steps x envs = {k * self.N} exceeds max_buffer_size = {self.cfg.max_buffer_size}: a launch may not '
+                             f'overwrite its own rows')
+        unmet = [why for ok, why in ((self._fused_collect, 'the agent on its fused path without running normalisers'),
+                                     (parallel.world_size() == 1, 'one rank'),
+                                     (getattr(self.env, 'sac_collect_supported', False),
+                                      "an env built with policy=(hidden_dim <= 128, activation, 'sac') (fused_rollout=True)")) if not ok]
+        if unmet:
+            warnings.warn(f'collect_steps={k} needs {"; ".join(unmet)}: keeping the stepwise collector')
+            return 0
+        return k
 
     # ---- hooks: every difference between the algorithms' trainers
+    CHUNKED_COLLECT = False             # whether `collect_steps` is served (SAC: scg_rollout_sac_collect)
+
     def _seed(self, seed):
         torch.manual_seed(seed)
 
@@ -457,16 +497,34 @@ class OffPolicyTrainer:
             st['g'] = g
         st['g'].replay()
 
+    def _collect_chunk(self, k, warm):
+        """The chunked collector: k vector steps in ONE launch (HipVecEnv.rollout_sac_collect), launched directly — there is nothing
+        for a graph to join.  Its action noise is addressed by the envs' own episode / step counters (which env_random_state carries):
+        `collect_counter` is neither read nor advanced here."""
+        buf = self.buffer
+        if self._chunk is None or self._chunk['of'] is not buf:
+            self._chunk = {'of': buf, 'actor': self.agent.actor_struct(),
+                           'c': {u: self.env.sac_collect_struct(buf, self.obs, uniform=u) for u in (False, True)}}
+        self.env.rollout_sac_collect(self._chunk['actor'], k, buf, self.obs, struct=self._chunk['c'][bool(warm)])
+
     def train_step(self, lazy=False):
-        """One vectorised env step (+ the gradient steps it owes).  lazy=True: the fused update's statistics are not read back
-        ('stats_dev' instead of floats) — with the graph-replayed collector the call then never waits for the GPU."""
+        """One vectorised env step (+ the gradient steps it owes) — or, with the chunked collector (`collect_steps`), the vector steps
+        up to the next point at which the stepwise schedule changes mode or owes an update (chunk_steps), in one launch.  lazy=True: the
+        fused update's statistics are not read back ('stats_dev' instead of floats) — with the graph-replayed collector the call then
+        never waits for the GPU."""
         cfg = self.cfg
         t0 = time.perf_counter()
-        self._collect(self.total_steps < cfg.warm_up_steps)
-        self.buffer.advance_host(self.N)
         world = parallel.world_size()
-        self.total_steps += self.N * world
-        self._since_update += self.N * world
+        warm = self.total_steps < cfg.warm_up_steps
+        k = 1
+        if self._collect_k and cfg.train_interval > self.N * world:        # (else every chunk has length 1: the stepwise path)
+            k = chunk_steps(self.total_steps, self._since_update, self.N * world, cfg.warm_up_steps, cfg.train_interval, self._collect_k)
+            self._collect_chunk(k, warm)
+        else:
+            self._collect(warm)
+        self.buffer.advance_host(k * self.N)
+        self.total_steps += k * self.N * world
+        self._since_update += k * self.N * world
         results = {}
         if self.total_steps > cfg.warm_up_steps and self._since_update >= cfg.train_interval:
             # the reference locks the ratio of gradient steps to env steps to 1 (sac.py:323-331); with N envs per

@@ -384,6 +384,11 @@ class SAC(OffPolicyTrainer):
     """SAC.train_step / learn on a HipVecEnv (sac.py:162-335): OffPolicyTrainer with a sampled action."""
     AGENT = SACAgent
     _graph_eager_collector = True       # sampling is torch.randn_like on the device: the PyTorch collector is capturable
+    # extra['collect_steps'] = K: up to K vector steps per launch into the replay ring (scg_rollout_sac_collect through
+    # OffPolicyTrainer._collect_chunk), on the stepwise update schedule (offpolicy.chunk_steps).  The chunked collector draws its
+    # action noise from the envs' Philox streams, the stepwise one from the agent's counter stream: the two train on different
+    # samples at the same seed
+    CHUNKED_COLLECT = True
 
     def _explore(self):
         return self.agent.ac.act(self.obs)

@@ -465,6 +465,36 @@ class HipVecEnv(VecEnv):
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_actor(self._h, C.byref(actor), int(k_steps), C.byref(o), self._stream()))
 
+    @property
+    def sac_collect_supported(self):
+        """Whether rollout_sac_collect is served: an env built with policy=(H, activation, 'sac'), H <= 128 (not the CBF library)."""
+        return self.actor_kind == 'sac' and self.policy_shape[0] != L.WIDE_HIDDEN and self.cbf_shape is None
+
+    def sac_collect_struct(self, ring, cur_obs, uniform=False, trace=None, episode_acc=None, max_episodes=0):
+        """The scg_sac_collect (_lib.SacCollect) of a replay ring (an object with obs / act / rew / next_obs / mask tensors, `capacity`
+        and the device scalars pos_t / size_t / size_i32: offpolicy.DeviceReplay), the collector's current-observation batch and, for
+        tests, trace = dict(obs=[k + 1, N, obs_dim], act=, reward=, done=, flags=, terminal_obs=) — all six or None."""
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        c = L.SacCollect(d_ring_obs=p(ring.obs), d_ring_act=p(ring.act), d_ring_rew=p(ring.rew), d_ring_next_obs=p(ring.next_obs),
+                         d_ring_mask=p(ring.mask), capacity=int(ring.capacity), d_pos=p(ring.pos_t), d_size_f=p(ring.size_t),
+                         d_size_i32=p(ring.size_i32), d_cur_obs=p(cur_obs), uniform=int(bool(uniform)), d_ep_stats=p(self.ep_stats),
+                         d_episode_acc=p(episode_acc), max_episodes=int(max_episodes))
+        for name, t in (trace or {}).items():
+            setattr(c, 'd_' + name, p(t))
+        return c
+
+    def rollout_sac_collect(self, actor, k_steps, ring, cur_obs, uniform=False, trace=None, episode_acc=None, max_episodes=0, struct=None):
+        """K vector steps of SAC's training collection in ONE launch (scg_rollout_sac_collect, include/scg_actor_collect.h): the
+        sampled actor (uniform=True: the warm-up's uniform action) inside the env kernel, every transition written into `ring`
+        with the time-limit fix-up, `cur_obs` [N, obs_dim] left at the observation after the last step, the ring's device counters
+        advanced by K N (the caller advances its host mirror).  `actor`: SACAgent.actor_struct().  struct: a prepared
+        sac_collect_struct(...) (the other ring arguments are then not read)."""
+        if self.actor_kind is None or not hasattr(self._lib, L.COLLECT_EXPORT):
+            raise L.ScgError("this env was not built with an actor kind (HipVecEnv(..., policy=(hidden, activation, 'sac')))")
+        c = struct if struct is not None else self.sac_collect_struct(ring, cur_obs, uniform, trace, episode_acc, max_episodes)
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_sac_collect(self._h, C.byref(actor), int(k_steps), C.byref(c), self._stream()))
+
     def rollout_cbf_actor(self, actor, params, k_steps, obs, act, reward, done, flags, filter_rows, applied, terminal_obs=None,
                           episode_acc=None, max_episodes=0):
         """rollout_actor with the CBF filter between the actor and the env step (scg_rollout_cbf_actor): `params` an _cbf.CbfParams;
