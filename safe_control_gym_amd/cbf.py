@@ -138,7 +138,7 @@ class CBF:
         a = a_in.to(device=venv.device, dtype=torch.float32).reshape(-1).contiguous()
         if a.numel() != s.shape[0]:
             raise ValueError(f'{s.shape[0]} states but {a.numel()} actions')
-        cert, _, feas = venv.certify_tensors(self.params(), s, a)
+        cert, _, feas = self.certify_tensors(s, a)
         if single:
             lo, hi = self.physical_action_bounds
             unc = np.clip(np.asarray(uncertified_action.cpu() if torch.is_tensor(uncertified_action) else uncertified_action, dtype=np.float64),
@@ -161,7 +161,7 @@ class CBF:
         venv = self._env()
         s = torch.as_tensor(states).to(device=venv.device, dtype=torch.float32)
         a = torch.ones(s.shape[0], device=venv.device, dtype=torch.float32)              # the reference's dummy control input
-        _, _, feas = venv.certify_tensors(self.params(), s, a)
+        _, _, feas = self.certify_tensors(s, a)
         bad = ~feas.bool().cpu().numpy()
         infeasible = states[bad]
         barrier = 1.0 - ((infeasible / np.asarray(self.state_limits, dtype=np.float64)) ** 2).sum(axis=1)

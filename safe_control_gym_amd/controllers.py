@@ -154,9 +154,13 @@ class HipController:
         ev = env if isinstance(env, HipVecEnv) else None
         if safety_filter is not None:
             if ev is None:
-                if getattr(self, '_run_env_cbf', None) is None or self._run_env_cbf.num_envs != n_episodes:
+                nn = hasattr(safety_filter, 'residual')                              # a cbf_nn.CBF_NN: its own library
+                cached = getattr(self, '_run_env_cbf', None)
+                if cached is None or cached.num_envs != n_episodes or (cached.cbf_nn_shape is not None) != nn:
+                    if cached is not None:
+                        cached.close()
                     self._run_env_cbf = HipVecEnv(self.env_id, n_episodes, seed=self.seed * 111, return_numpy=False, policy=self._policy_shape(),
-                                                  cbf=True, **self.task_config)
+                                                  cbf=not nn, cbf_nn=nn, **self.task_config)
                 ev = self._run_env_cbf
             if getattr(self, 'norm_obs', False) or not getattr(self.impl, '_fused_rollout', False):
                 raise L.ScgError('run(safety_filter=) needs the fused rollout path without observation normalisation')

@@ -1,7 +1,8 @@
-// scg_cbf_core.h — the CBF-QP safety filter (include/scg_cbf.h), one copy for both CBF libraries: the closed form of the QP as a
-// device function, the batched certify kernel, the parameter checks, the filter functor of the SAC / DDPG actor rollouts, and the
-// entry points that do not depend on the rollout kernel (scg_cbf_shape, scg_cbf_certify).  Included by scg_cbf.hip and
-// scg_cbf_wide.hip behind the simulator's translation unit; the includer names the actor shape its library was compiled for:
+// scg_cbf_core.h — the CBF-QP safety filter (include/scg_cbf.h), one copy for every CBF library: the closed form of the QP as device
+// functions (cbf_row: the barrier row; cbf_solve: its minimiser; cbf_certify: their composition; cbf_nn_certify: the row with a learned
+// residual added, include/scg_cbf_nn.h), the batched certify kernel, the parameter checks, the filter functor of the SAC / DDPG actor
+// rollouts, and the entry points that do not depend on the rollout kernel (scg_cbf_shape, scg_cbf_certify).  Included by scg_cbf.hip,
+// scg_cbf_wide.hip and scg_cbf_nn.hip behind the simulator's translation unit; the includer names the actor shape its library was compiled for:
 //   SCG_CBF_HIDDEN, SCG_CBF_ACTIVATION     what scg_cbf_shape reports
 // The filter serves float32 CartPole configs (SCG_CBF_SERVED); any other library exports the entry points and refuses.
 #pragma once
@@ -20,9 +21,11 @@ namespace scg {
 
 struct CbfResult { float u0, u, s, feasible; };
 
-// The closed-form minimiser of the reference's CBF-QP (include/scg_cbf.h) for one (state, physical action).  Every operation is an
-// explicitly rounded float32 one (no contraction), so every kernel that calls it agrees bit for bit.
-__device__ __forceinline__ CbfResult cbf_certify(const scg_cbf_params& p, const float* X, float u_phys) {
+struct CbfRow { float k, b; };
+
+// The barrier row of the reference's CBF-QP (include/scg_cbf.h) at one state: r(u) = -k - b u.  Every operation here and in cbf_solve
+// is an explicitly rounded float32 one (no contraction), so every kernel that calls them agrees bit for bit.
+__device__ __forceinline__ CbfRow cbf_row(const scg_cbf_params& p, const float* X) {
     // barrier and its gradient
     float h = 1.0f, gr[4];
 #pragma unroll
@@ -44,7 +47,14 @@ __device__ __forceinline__ CbfResult cbf_certify(const scg_cbf_params& p, const 
     const float dxdd = __fsub_rn(dtmp, __fdiv_rn(__fmul_rn(__fmul_rn(ml, dthdd), cs), Mm));
     const float a = __fadd_rn(__fadd_rn(__fmul_rn(gr[0], X[1]), __fmul_rn(gr[1], xdd0)), __fadd_rn(__fmul_rn(gr[2], X[3]), __fmul_rn(gr[3], thdd0)));
     const float b = __fadd_rn(__fmul_rn(gr[1], dxdd), __fmul_rn(gr[3], dthdd));
-    const float k = __fadd_rn(__fmul_rn(p.slope, h), a);
+    CbfRow r;
+    r.k = __fadd_rn(__fmul_rn(p.slope, h), a);
+    r.b = b;
+    return r;
+}
+
+// The closed-form minimiser of the QP with the row (k, b) for one physical action.
+__device__ __forceinline__ CbfResult cbf_solve(const scg_cbf_params& p, float k, float b, float u_phys) {
     CbfResult o;
     o.u0 = fminf(fmaxf(u_phys, p.lo), p.hi);
     const float r0 = __fsub_rn(-k, __fmul_rn(b, o.u0));
@@ -64,6 +74,19 @@ __device__ __forceinline__ CbfResult cbf_certify(const scg_cbf_params& p, const 
         }
     }
     return o;
+}
+
+// The filter for one (state, physical action): the row, then its minimiser.
+__device__ __forceinline__ CbfResult cbf_certify(const scg_cbf_params& p, const float* X, float u_phys) {
+    const CbfRow r = cbf_row(p, X);
+    return cbf_solve(p, r.k, r.b, u_phys);
+}
+
+// The same with a learned correction of the Lie derivative (safety_filters/cbf/cbf_nn.py:104-124): the barrier row becomes
+// -slope h - LfV(X, u) - (a_nn u + b_nn) <= s, which is the QP above with k' = k + b_nn and b' = b + a_nn (include/scg_cbf_nn.h).
+__device__ __forceinline__ CbfResult cbf_nn_certify(const scg_cbf_params& p, const float* X, float u_phys, float a_nn, float b_nn) {
+    const CbfRow r = cbf_row(p, X);
+    return cbf_solve(p, __fadd_rn(r.k, b_nn), __fadd_rn(r.b, a_nn), u_phys);
 }
 
 __global__ __launch_bounds__(256) void cbf_certify_kernel(const scg_cbf_params p, const float* __restrict__ state, const float* __restrict__ action,

@@ -1059,7 +1059,13 @@ def _evaluate_cbf_device(env, policy, safety_filter, episodes_per_env=1):
     env.reset_tensors()
     buf['acc'].zero_()
     from safe_control_gym_amd import _lib as L
-    if isinstance(policy, L.Actor):                 # a deterministic SAC / DDPG actor (scg_rollout_cbf_actor)
+    if getattr(env, 'cbf_nn_shape', None) is not None:      # a cbf_nn.CBF_NN: scg_rollout_cbf_nn with the evaluation rule (blend = -1)
+        if 'ab' not in buf:
+            buf['ab'] = torch.zeros(steps, N, 2, device=dev, dtype=torch.float32)
+        env.rollout_cbf_nn(_cbf.actor_ptrs_of_policy(policy), safety_filter.params(), safety_filter.residual(dev), steps, buf['obs'],
+                           buf['act'], buf['logp'], buf['rew'], buf['done'], buf['flags'], buf['rows'], buf['applied'], buf['ab'],
+                           deterministic=True, blend=-1.0, episode_acc=buf['acc'], max_episodes=episodes_per_env)
+    elif isinstance(policy, L.Actor):               # a deterministic SAC / DDPG actor (scg_rollout_cbf_actor)
         env.rollout_cbf_actor(policy, safety_filter.params(), steps, buf['obs'], buf['act'], buf['rew'], buf['done'], buf['flags'],
                               buf['rows'], buf['applied'], episode_acc=buf['acc'], max_episodes=episodes_per_env)
     else:
@@ -1157,8 +1163,15 @@ def evaluate(ac, env, episodes_per_env=1, use_graph=None, obs_normalizer=None, p
     steps = env.spec.max_episode_steps * episodes_per_env
     dev = env.device
     if safety_filter is not None:
-        if policy is None or obs_normalizer is not None or getattr(env, 'cbf_shape', None) is None:
-            from safe_control_gym_amd import _lib as L
+        from safe_control_gym_amd import _lib as L
+        if hasattr(safety_filter, 'residual'):      # a cbf_nn.CBF_NN
+            if isinstance(policy, L.Actor):
+                raise L.ScgError('no SAC / DDPG actor in front of the cbf_nn filter: a 256-wide actor and the residual network do not share '
+                                 'a register file')
+            if policy is None or obs_normalizer is not None or getattr(env, 'cbf_nn_shape', None) is None:
+                raise L.ScgError('evaluate(safety_filter=) with a cbf_nn filter needs an env built with policy=(hidden, activation), '
+                                 'cbf_nn=True, the policy struct of that shape and no observation normaliser')
+        elif policy is None or obs_normalizer is not None or getattr(env, 'cbf_shape', None) is None:
             raise L.ScgError('evaluate(safety_filter=) needs an env built with policy=(hidden, activation), cbf=True, the policy struct of '
                              'that shape and no observation normaliser: the filtered evaluation exists only as the fused launch')
         res, a, data = _evaluate_cbf_device(env, policy, safety_filter, episodes_per_env)

@@ -111,9 +111,11 @@ for _idx, _cls in (('ppo', 'PPO'), ('sac', 'SAC'), ('ddpg', 'DDPG'), ('rarl', 'R
     register(idx=_idx, entry_point=f'safe_control_gym_amd.controllers:{_cls}',
              config_entry_point=f'safe_control_gym_amd.controllers:{_idx.upper()}_DEFAULTS')
 
-# safety-filter ids of the reference (safety_filters/__init__.py registers 'cbf', 'cbf_nn', 'linear_mpsc'): the analytic CBF-QP filter;
-# 'cbf_nn' (a 256 x 256 residual network) and 'linear_mpsc' (an MPC solve per step) are out of scope
+# safety-filter ids of the reference (safety_filters/__init__.py registers 'cbf', 'cbf_nn', 'linear_mpsc'): the analytic CBF-QP filter
+# and the same QP with a learned correction of the Lie derivative (a 256 x 256 residual network on the row-split forward pass,
+# csrc/scg_cbf_nn.hip); 'linear_mpsc' (an MPC solve per step) is out of scope
 register(idx='cbf', entry_point='safe_control_gym_amd.cbf:CBF', config_entry_point='safe_control_gym_amd.cbf:CBF_DEFAULTS')
+register(idx='cbf_nn', entry_point='safe_control_gym_amd.cbf_nn:CBF_NN', config_entry_point='safe_control_gym_amd.cbf_nn:CBF_NN_DEFAULTS')
 
 # baseline controller ids of the reference (controllers/__init__.py: 'lqr', 'ilqr', 'pid'), batched: one closed-loop launch per rollout,
 # one backward-pass launch per iLQR iteration (lqr.py, csrc/scg_ilqr.hip); 'pid' (pid.py, csrc/scg_pid.h) is the quadrotor-only cascade

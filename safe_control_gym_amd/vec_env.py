@@ -200,7 +200,7 @@ class HipVecEnv(VecEnv):
     """N independent copies of one environment stepped by libscg_hip.so on one GPU."""
 
     def __init__(self, env_id, num_envs, seed=0, device=None, dtype=torch.float32, env_id_offset=0,
-                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, safety_layer=None, cbf=False, ilqr=False, **task_config):
+                 return_numpy=True, auto_reset=True, specialize='auto', policy=None, adversaries=None, safety_layer=None, cbf=False, ilqr=False, cbf_nn=False, **task_config):
         L.lib()                                        # fail loudly, before touching torch.cuda
         if not torch.cuda.is_available():
             raise L.ScgError('HipVecEnv needs a HIP device (torch.cuda.is_available() is False); '
@@ -280,10 +280,26 @@ class HipVecEnv(VecEnv):
             if not served:
                 raise L.ScgError('cbf=True needs a float32 env and policy=(hidden, activation) of a shape the fused policy rollout serves')
             self.cbf_shape = self.policy_shape
+        # cbf_nn=True (with policy=(hidden, activation)): the library of the CBF filter with the learned Lie-derivative residual
+        # (certify_nn_tensors / rollout_cbf_nn below; include/scg_cbf_nn.h).  PPO's actor shapes on the cartpole only; no fallback
+        self.cbf_nn_shape = None
+        if cbf_nn:
+            from safe_control_gym_amd import _cbf_nn
+            if cbf or adversaries is not None or safety_layer is not None:
+                raise ValueError('cbf_nn=True cannot be combined with cbf=, adversaries= or safety_layer=')
+            if env_id != 'cartpole':
+                raise NotImplementedError('[Error] Currently CBF is only implemented for the cartpole system.')
+            if policy is not None and len(policy) == 3:
+                raise L.ScgError('cbf_nn=True serves PPO\'s actor (policy=(hidden, activation)): no SAC / DDPG actor in front of this filter '
+                                 '(a 256-wide actor and the residual network do not share a register file)')
+            if self.policy_shape is None or not _cbf_nn.supported(env_id, spec.obs_dim, self.policy_shape[0], spec.nu, self.policy_shape[1]):
+                raise L.ScgError('cbf_nn=True needs a float32 env and policy=(hidden, activation) of a shape the fused policy rollout serves '
+                                 'whose LDS image fits beside the residual network\'s')
+            self.cbf_nn_shape = self.policy_shape
         # ilqr=True: the library that also carries the LQR / iLQR controllers' kernels (rollout_feedback / ilqr_backward below)
         self.ilqr = bool(ilqr)
-        if self.ilqr and (policy is not None or adversaries is not None or safety_layer is not None or cbf):
-            raise ValueError('ilqr=True cannot be combined with policy=, adversaries=, safety_layer= or cbf=')
+        if self.ilqr and (policy is not None or adversaries is not None or safety_layer is not None or cbf or cbf_nn):
+            raise ValueError('ilqr=True cannot be combined with policy=, adversaries=, safety_layer=, cbf= or cbf_nn=')
         if self.ilqr:
             from safe_control_gym_amd import _ilqr
             self._lib, self.specialized = _ilqr.lib_for(cfg), True
@@ -291,6 +307,8 @@ class HipVecEnv(VecEnv):
             self._lib, self.specialized = _adversarial.lib_for(cfg, *self.adversary_shape), True
         elif self.cbf_shape is not None:
             self._lib, self.specialized = _cbf.lib_for(cfg, *self.cbf_shape), True
+        elif self.cbf_nn_shape is not None:
+            self._lib, self.specialized = _cbf_nn.lib_for(cfg, *self.cbf_nn_shape), True
         elif self.safety_shape is not None:
             from safe_control_gym_amd import _safe_explorer
             self._lib, self.specialized = _safe_explorer.lib_for(cfg, *self.safety_shape), True
@@ -642,6 +660,63 @@ class HipVecEnv(VecEnv):
         with torch.cuda.device(self.device):
             self._chk(self._lib.scg_rollout_cbf(self._h, C.byref(actor), C.byref(params), int(bool(deterministic)), int(k_steps), C.byref(o),
                                                 p(filter_rows), p(applied), self._stream()))
+
+    def certify_nn_tensors(self, params, residual, states, actions, certified=None, slack=None, feasible=None, ab=None):
+        """certify_tensors with the learned residual (scg_cbf_nn_certify): `residual` an _cbf_nn.Residual whose flat parameter tensor the
+        caller keeps alive; additionally returns (and fills, when passed) ab [n, 2] float32 = (a_nn, b_nn) of every row."""
+        if self.cbf_nn_shape is None:
+            raise L.ScgError('this env was not built with the cbf_nn filter (HipVecEnv(..., policy=(hidden, activation), cbf_nn=True))')
+        if states.dim() != 2 or states.shape[1] != 4 or actions.shape != (states.shape[0],):
+            raise ValueError('states must be [n, 4] and actions [n]')
+        n = int(states.shape[0])
+        f = dict(dtype=torch.float32, device=self.device)
+        certified = torch.empty(n, **f) if certified is None else certified
+        slack = torch.empty(n, **f) if slack is None else slack
+        feasible = torch.empty(n, dtype=torch.uint8, device=self.device) if feasible is None else feasible
+        ab = torch.empty(n, 2, **f) if ab is None else ab
+        for t, dt in ((states, torch.float32), (actions, torch.float32), (certified, torch.float32), (slack, torch.float32),
+                      (ab, torch.float32), (feasible, torch.uint8)):
+            if t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('states, actions, certified, slack, ab (float32) and feasible (uint8) must be contiguous tensors on the env device')
+        if certified.numel() != n or slack.numel() != n or feasible.numel() != n or ab.numel() != 2 * n:
+            raise ValueError(f'certified, slack and feasible must hold {n} entries and ab {2 * n}')
+        if n == 0:                                   # (empty tensors have no pointers to hand over; the entry point's n = 0 is a no-op too)
+            return certified, slack, feasible, ab
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_cbf_nn_certify(self._h, C.byref(params), C.byref(residual), p(states), p(actions), p(certified), p(slack),
+                                                   p(feasible), p(ab), n, self._stream()))
+        return certified, slack, feasible, ab
+
+    def rollout_cbf_nn(self, actor, params, residual, k_steps, obs, act, logp, reward, done, flags, filter_rows, applied, ab,
+                       deterministic=False, uniform=False, blend=-1.0, terminal_obs=None, episode_acc=None, max_episodes=0):
+        """K control steps in ONE launch with PPO's actor, the residual network AND the filter in the loop (scg_rollout_cbf_nn): `actor`
+        an _adversarial.ActorPtrs (None with uniform=True: the uncertified action is action_space.sample() from Philox channel 4),
+        `params` an _cbf.CbfParams, `residual` an _cbf_nn.Residual.  blend < 0: the evaluation rule (u* where feasible, else the policy's
+        own action); 0 <= blend <= 1: applied = (1 - blend) a + blend u*_env.  filter_rows [K, N, 4], applied [K, N] and ab [K, N, 2]
+        receive every step's (u0, u*, s*, feasible), applied action and (a_nn, b_nn); the other arguments are as for rollout_policy."""
+        from safe_control_gym_amd import _cbf_nn
+        if self.cbf_nn_shape is None:
+            raise L.ScgError('this env was not built with the cbf_nn filter (HipVecEnv(..., policy=(hidden, activation), cbf_nn=True))')
+        k = int(k_steps)
+        if filter_rows.shape != (k, self.num_envs, 4) or applied.shape != (k, self.num_envs) or ab.shape != (k, self.num_envs, 2):
+            raise ValueError(f'filter_rows must be [{k}, {self.num_envs}, 4], applied [{k}, {self.num_envs}] and ab [{k}, {self.num_envs}, 2]')
+        for t in (filter_rows, applied, ab):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('filter_rows, applied and ab must be contiguous float32 tensors on the env device')
+        if actor is None and not uniform:
+            raise ValueError('rollout_cbf_nn needs an actor unless uniform=True')
+        o = L.PolicyRollout()
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+        o.d_obs, o.d_act, o.d_logp, o.d_reward, o.d_done, o.d_flags = p(obs), p(act), p(logp), p(reward), p(done), p(flags)
+        o.d_terminal_obs, o.d_ep_stats, o.d_episode_acc = p(terminal_obs), p(self.ep_stats), p(episode_acc)
+        o.max_episodes = int(max_episodes)
+        space = self.spec.action_space
+        mode = _cbf_nn.Mode(deterministic=int(bool(deterministic)), uniform=int(bool(uniform)), act_low=float(space.low.reshape(-1)[0]),
+                            act_high=float(space.high.reshape(-1)[0]), blend=float(blend))
+        with torch.cuda.device(self.device):
+            self._chk(self._lib.scg_rollout_cbf_nn(self._h, C.byref(actor) if actor is not None else None, C.byref(params), C.byref(residual),
+                                                   C.byref(mode), k, C.byref(o), p(filter_rows), p(applied), p(ab), self._stream()))
 
     def rollout_feedback(self, gains, ff, k_steps, x, u, final_obs, stats, n_steps, final_flags, per_env=False, reward=None, done=None,
                          flags=None):
