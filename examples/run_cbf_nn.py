@@ -36,6 +36,7 @@ def main():
     ap.add_argument('--random-actions', action='store_true', help='learn with action_space.sample() instead of the PPO controller')
     ap.add_argument('--load', default=None, help='a checkpoint written by --save: skip learn()')
     ap.add_argument('--save', default=None)
+    ap.add_argument('--fused-update', action='store_true', help='the Adam steps in scg_cbf_nn_update, one call per episode (fused_update=True)')
     a = ap.parse_args()
     S = json.load(open(os.path.join(GOLDEN, 'cbf_nn_settings.json')))               # the example's task and filter settings
     D = np.load(os.path.join(GOLDEN, 'cbf.npz'))                                    # the example's shipped actor, as arrays
@@ -52,6 +53,8 @@ def main():
     sf_config = dict(S['sf_config'])
     if a.episodes is not None:
         sf_config['num_episodes'] = a.episodes
+    if a.fused_update:
+        sf_config['fused_update'] = True
     env_func = partial(make, S['task'], **cfg)
     sf = make(S['safety_filter'], env_func, seed=a.seed, policy=shape, **sf_config)
     if a.load:
