@@ -9,7 +9,7 @@ from safe_control_gym_amd import _shapelib
 from safe_control_gym_amd._learn import ACTS, MlpLayout
 
 SRC = os.path.join(L.CSRC_DIR, 'scg_sac.hip')
-DEPS = [SRC] + [os.path.join(L.CSRC_DIR, h) for h in ('scg_wide.h', 'scg_adam.h', 'scg_mlp.h', 'scg_once.h', 'scg_rng.h')] + \
+DEPS = [SRC] + [os.path.join(L.CSRC_DIR, h) for h in ('scg_wide.h', 'scg_offpolicy_step.h', 'scg_adam.h', 'scg_mlp.h', 'scg_once.h', 'scg_rng.h')] + \
     [os.path.normpath(os.path.join(L.CSRC_DIR, '..', '..', 'include', h)) for h in ('scg_sac.h', 'scg_learn.h')]
 
 

@@ -7,7 +7,9 @@
 // same wide-tile scheme (scg_wide.h; measured for this launch shape in scg_sac.hip's notes): 32-sample column tiles, one tile per
 // workgroup, the hidden features split over the workgroup's waves, the activation tiles of a forward pass that feeds a gradient
 // kernel stored write-through for it, one partial gradient vector per workgroup summed in a fixed order by the reduction launch
-// (which also runs Adam and the Polyak update of each parameter it owns).
+// (which also runs Adam and the Polyak update of each parameter it owns).  q_kernel, the pairing of the reduction's group sums and
+// the host helpers are SAC's own, from scg_offpolicy_step.h; this file keeps the deterministic actor's kernels, the reduction's group
+// sums and bookkeeping, and the collector.
 //   actor_fwd_kernel  rows ~ U[0, ring size); a = actor(obs) + its h1 / h2 tiles and tanh outputs          compute_policy_loss
 //   q_kernel<1>       q(obs, a), dq/da
 //   actor_grad_kernel d(-mean q)/d(actor) from the stored pass
@@ -58,17 +60,11 @@ extern "C" void scg_ddpg_shape(int32_t* nobs, int32_t* hidden, int32_t* nu, int3
 extern "C" const char* scg_ddpg_source_hash_tag(void) { return "SCG_SRC_HASH:" SCG_STR(SCG_SRC_HASH); }
 #define HIP_TRY(e) do { hipError_t _e = (e); if (_e != hipSuccess) return fail(-2, std::string(#e) + ": " + hipGetErrorString(_e)); } while (0)
 
+#include "scg_offpolicy_step.h"
+
 // ================================================================== gradient step
 namespace scg {
 namespace wide {
-
-struct Common {
-    const int32_t* idx; int batch; int n_part;
-    const float* obs; const float* act; const float* rew; const float* next_obs; const float* mask;
-    float low[4], high[4];
-    float gamma;
-    uint32_t k0, k1; const uint32_t* counter;
-};
 
 // One actor forward job: rows `idx` (or, with idx_out, drawn here and kept for the later launches) of `src`; the action per batch
 // row; optionally (th / h1s / h2s) what actor_grad_kernel needs of this pass.
@@ -123,133 +119,24 @@ __global__ __launch_bounds__(64 * NT, 2) void actor_fwd_kernel(const float* __re
                 if (J.th) J.th[(size_t)j * B + r] = th;
             }
         }
-        __syncthreads();                                                // the exchange buffers are free for the next tile
+        // (no barrier here: forward()'s two keep a tile's exchange buffers from the next tile's writes — the argument stands above
+        //  QAct in scg_offpolicy_step.h)
     }
 }
 
-// The critic.
-//   MODE 0: forward only, blockIdx.y = online:
-//             0: TARGET critic at (next_obs[idx], a_in[row])       -> q_out[row]
-//             1: ONLINE critic at (obs[idx], act[idx])             -> qo[row], the waves' h1 / h2 tiles, reward and mask, for MODE 2
-//   MODE 1: online critic at (obs[idx], a_in[row]) + data gradient -> q_out[row], dqda[row][NU]
-//   MODE 2: backward only: d mean (q - y)^2 / d(theta) into the workgroups' partials, q = qo[row] and the stored tiles,
-//           y = rew + gamma mask q_targ[row]
-struct QAct { float* qo; float* h1s; float* h2s; float* rew; float* mask; };
-template <int MODE>
-__global__ __launch_bounds__(64 * NT, MODE == 0 ? 2 : 1) void q_kernel(const float* __restrict__ params, const float* __restrict__ params_online,
-                                                                     const scg_mlp_layout lay, const Common Cm, const float* __restrict__ a_in,
-                                                                     const float* __restrict__ qt, float* __restrict__ q_out,
-                                                                     float* __restrict__ dqda, const QAct QA, float* __restrict__ partials) {
-    using S = Small<1>;
-    using G = Part<NQ, 1>;
-    constexpr int L1Q = 4 * ((NQ + 7) / 8);
-    extern __shared__ __align__(16) float lds[];
-    const bool online = MODE == 0 && blockIdx.y;
-    const MlpWeights w = weights_of(online ? params_online : params, lay);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-    const int n_tiles = Cm.batch / 32;
-    const int tile0 = blockIdx.x, r0 = tile0 * 32 + c;
-    const int s0 = Cm.idx[r0];
-    SmallRegs<1> sr;
-    small_load<1>(sr, w, threadIdx.x);
-    float* const xch = lds + S::END;
-    if constexpr (MODE == 2) {
-        float bt[NT][16];
-        f32x16 h1, h2;
-        float x[L1Q], v_rew = 0.0f, v_mask = 0.0f, v_qt = 0.0f, v_q = 0.0f;
-        auto load_row = [&](int tile, int r) {
-            act_load(QA.h1s, tile, wave, lane, h1); act_load(QA.h2s, tile, wave, lane, h2);
-            v_q = QA.qo[r]; v_qt = qt[r]; v_rew = QA.rew[r]; v_mask = QA.mask[r];
-        };
-        auto load_in = [&](int s) { load_x2<L1Q, NOBS, NU>(Cm.obs + (size_t)s * NOBS, Cm.act + (size_t)s * NU, h, x); };
-        load_row(tile0, r0);
-        load_bt(w.W2, wave, lane, bt);
-        load_in(s0);
-        small_store<1>(lds, sr, threadIdx.x);
-        __syncthreads();
-        float* const P = partials + (size_t)blockIdx.x * PSTRIDE;
-        const float inv_b = 1.0f / (float)Cm.batch;
-        float st = 0.0f;
-        bool first = true;
-        for (int tile = tile0; tile < n_tiles; tile += gridDim.x) {
-            const int r = tile * 32 + c;
-            if (tile != tile0) { load_row(tile, r); load_in(Cm.idx[r]); }
-            const float target = v_rew + Cm.gamma * v_mask * v_qt;
-            const float e = v_q - target;
-            const float dout[1] = {2.0f * e * inv_b};
-            if (wave == 0 && h == 0) st += e * e * inv_b;
-            backward<NQ, 1, ACT, true, false>(lds, xch, bt, h1, h2, dout, wave, lane, P, first, nullptr, x);
-            first = false;
-            __syncthreads();
-        }
-        if (wave == 0) {
-            const float v = row_sum32(xch + Xch::WAVE + TR_WORDS + 34 * 32, st, lane);
-            if (lane == 0) { P[G::STAT] = v; P[G::STAT + 1] = 0.0f; }
-        }
-    } else {
-        float w1a[(NU * HID + 64 * NT - 1) / (64 * NT)];
-        if constexpr (MODE == 1) {                                      // W1A[j][f] = W1[f][NOBS + j]
-#pragma unroll
-            for (int j = 0; j < (NU * HID + 64 * NT - 1) / (64 * NT); ++j) {
-                const int k = threadIdx.x + j * 64 * NT;
-                w1a[j] = k < NU * HID ? w.W1[(size_t)(k % HID) * NQ + NOBS + k / HID] : 0.0f;
-            }
-        }
-        float a1[L1Q], a2[NT][16];
-        load_a1<NQ, L1Q>(w.W1, wave, lane, a1);
-        load_a2(w.W2, wave, lane, a2);
-        float x[L1Q], v_rew = 0.0f, v_mask = 0.0f;
-        auto load_row = [&](int r, int s) {
-            if constexpr (MODE == 0) {
-                if (online) {
-                    load_x2<L1Q, NOBS, NU>(Cm.obs + (size_t)s * NOBS, Cm.act + (size_t)s * NU, h, x);
-                    v_rew = Cm.rew[s]; v_mask = Cm.mask[s];
-                } else load_x2<L1Q, NOBS, NU>(Cm.next_obs + (size_t)s * NOBS, a_in + (size_t)r * NU, h, x);
-            } else {
-                load_x2<L1Q, NOBS, NU>(Cm.obs + (size_t)s * NOBS, a_in + (size_t)r * NU, h, x);
-            }
-        };
-        load_row(r0, s0);
-        small_store<1>(lds, sr, threadIdx.x);
-        if constexpr (MODE == 1) {
-#pragma unroll
-            for (int j = 0; j < (NU * HID + 64 * NT - 1) / (64 * NT); ++j) {
-                const int k = threadIdx.x + j * 64 * NT;
-                if (k < NU * HID) lds[S::W1A + k] = w1a[j];
-            }
-        }
-        __syncthreads();
-        float bt[MODE == 1 ? NT : 1][16];
-        if constexpr (MODE == 1) load_bt(w.W2, wave, lane, bt);
-        for (int tile = tile0; tile < n_tiles; tile += gridDim.x) {
-            const int r = tile * 32 + c;
-            if (tile != tile0) load_row(r, Cm.idx[r]);
-            f32x16 h1, h2;
-            float out[1];
-            forward<NQ, 1, ACT>(lds, xch, a1, a2, x, wave, lane, h1, h2, out);
-            if constexpr (MODE == 0) {
-                if (online) {
-                    act_store(QA.h1s, tile, wave, lane, h1);
-                    act_store(QA.h2s, tile, wave, lane, h2);
-                    if (wave == 0 && h == 0) QA.qo[r] = out[0];
-                    if (wave == 1 % NT && h == 0) { QA.rew[r] = v_rew; QA.mask[r] = v_mask; }
-                } else if (wave == 0 && h == 0) {
-                    q_out[r] = out[0];
-                }
-            } else {
-                const float dout[1] = {1.0f};
-                float din[NU];
-                backward<NQ, 1, ACT, false, true>(lds, xch, bt, h1, h2, dout, wave, lane, nullptr, true, din);
-                if (wave == 0 && h == 0) {
-                    q_out[r] = out[0];
-#pragma unroll
-                    for (int j = 0; j < NU; ++j) dqda[(size_t)r * NU + j] = din[j];
-                }
-            }
-            __syncthreads();                                            // the exchange buffers are free for the next tile
-        }
-    }
-}
+// The critic's side of q_kernel (scg_offpolicy_step.h): one of them, target = rew + gamma mask q_targ[row].
+struct DdpgCritic {
+    static constexpr int NCRIT = 1;
+    struct Nets { scg_mlp_layout lay; };
+    static __device__ __forceinline__ const scg_mlp_layout& layout(const Nets& N, int) { return N.lay; }
+    struct TgtArgs { const float* __restrict__ qt; };                           // [B]
+    struct Tgt {
+        float qt = 0.0f;
+        __device__ __forceinline__ void load(const TgtArgs& A, int r, int) { qt = A.qt[r]; }
+        __device__ __forceinline__ void init(const Common&) {}
+        __device__ __forceinline__ float value(const Common& Cm, float v_rew, float v_mask) const { return v_rew + Cm.gamma * v_mask * qt; }
+    };
+};
 
 // actor gradient of policy_loss = -mean q(obs, actor(obs)), from the pass actor_fwd_kernel left behind (tiles, tanh outputs) and
 // q_kernel<1>'s q and dq/da:  d loss / d out_j = -(1/B) dq/da_j 0.5 (high_j - low_j)(1 - tanh^2)
@@ -343,6 +230,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceArgs R) {
             }
         }
     }
+    // (this loop is word for word scg_sac.hip's reduce_kernel's and must stay so — the order is the bitwise contract; why it is not a
+    //  shared device function is said there.  The pairing behind the barrier is pair_sum, scg_offpolicy_step.h.)
     float s = 0.0f;
     if (k < words) {
         const float* const src = R.partials + (size_t)grp * PSTRIDE + k;          // partials grp, grp + 4, ...
@@ -358,7 +247,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceArgs R) {
     part[grp][kl] = s;
     __syncthreads();
     if (!owner) return;
-    s = (part[0][kl] + part[1][kl]) + (part[2][kl] + part[3][kl]);
+    s = pair_sum(&part[0][kl], sizeof part[0] / sizeof part[0][0]);
     if (d >= 0) {
         R.grad[d] = s;
         adam_element(o_p, s, o_m, o_v, R.lr, R.critic ? o_s0 : o_s0 + 1.0f);
@@ -377,7 +266,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceArgs R) {
     }
 }
 
-// ------------------------------------------------------------------ host side of the step
+// ------------------------------------------------------------------ host side of the step (with the helpers of scg_offpolicy_step.h)
+using QC = wide::DdpgCritic;
 struct Ws {      // workspace carve-up (floats)
     size_t idx[2], a_pi, th, ah1, ah2, qpi, dqda, a_next, qt, qo, qh1, qh2, qrew, qmask, stat, partials, total;
 };
@@ -393,23 +283,11 @@ static Ws carve(int B, int n_part) {
     w.total = o;
     return w;
 }
-static int n_part_of(int batch) { const int t = batch / 32; return t < 512 ? t : 512; }
 
 extern "C" size_t scg_ddpg_workspace_bytes(int batch) {
     if (batch <= 0 || batch % 32) return 0;
     return carve(batch, n_part_of(batch)).total * sizeof(float);
 }
-
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-    HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
-
-static size_t wide_lds_actor() { return (wide::Small<NA>::END + wide::Xch::END) * sizeof(float); }
-static size_t wide_lds_q() { return (wide::Small<1>::END + wide::Xch::END) * sizeof(float); }
-static size_t wide_lds_actor_fwd() { return (wide::Small<NA>::END + wide::Xch::FWD_END) * sizeof(float); }
-static size_t wide_lds_q_fwd() { return (wide::Small<1>::END + wide::Xch::FWD_END) * sizeof(float); }
 
 // ================================================================== collector: noisy action, ring push
 constexpr int NCHUNK = 256;                     // envs per workgroup of the noisy-action launch (one per thread)
@@ -537,12 +415,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void noisy_act_kernel(const float* _
 struct CommitArgs { double* x_prev; const double* x_next; int64_t* calls; int32_t* pending; int kind; };
 __global__ void bookkeeping_kernel(const RingArgs R, int with_ring, int n, const CommitArgs Cn) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (with_ring) {
-        *R.pos = (*R.pos + n) % R.capacity;
-        if (R.size_f) *R.size_f = fminf(*R.size_f + (float)n, (float)R.capacity);
-        if (R.size_i) *R.size_i = min(*R.size_i + n, R.capacity);
-        if (R.counter) *R.counter += 1u;
-    }
+    if (with_ring) ring_advance(R, n);
     if (Cn.pending) {
         const int p = *Cn.pending;
         if (p > 0) {
@@ -564,16 +437,8 @@ extern "C" int scg_ddpg_prepare(void) {
         return fail(-1, "scg_ddpg: network image does not fit the LDS");
     if (set_lds(noisy_act_kernel, lds_noisy_bytes())) return -2;
     if (set_lds(wide::actor_fwd_kernel, wide_lds_actor_fwd()) || set_lds(wide::actor_grad_kernel, wide_lds_actor()) ||
-        set_lds(wide::q_kernel<0>, wide_lds_q_fwd()) || set_lds(wide::q_kernel<1>, wide_lds_q()) || set_lds(wide::q_kernel<2>, wide_lds_q())) return -2;
+        set_lds(wide::q_kernel<0, QC>, wide_lds_q_fwd()) || set_lds(wide::q_kernel<1, QC>, wide_lds_q()) || set_lds(wide::q_kernel<2, QC>, wide_lds_q())) return -2;
     once.commit(dev);
-    return 0;
-}
-
-static int check_args(const scg_ddpg_args* a, const char* who) {
-    if (!a || !a->d_params || !a->d_target || !a->d_grad || !a->d_m || !a->d_v || !a->d_steps || !a->d_obs || !a->d_act || !a->d_rew ||
-        !a->d_next_obs || !a->d_mask || !a->d_counter || !a->d_workspace || !a->d_stats || (!a->d_ring_size && !a->d_idx_in))
-        return fail(-1, std::string(who) + ": NULL argument");
-    if (a->batch <= 0 || a->batch % 32) return fail(-1, std::string(who) + ": the batch size must be a positive multiple of 32");
     return 0;
 }
 
@@ -586,10 +451,7 @@ static int enqueue_step(const scg_ddpg_args* a, hipStream_t st, int parity, bool
     int32_t* idx = (int32_t*)(W + w.idx[parity]);
     int32_t* idx_next = (int32_t*)(W + w.idx[parity ^ 1]);
     wide::Common Cm;
-    Cm.idx = idx; Cm.batch = B; Cm.n_part = n_part; Cm.obs = a->d_obs; Cm.act = a->d_act; Cm.rew = a->d_rew; Cm.next_obs = a->d_next_obs;
-    Cm.mask = a->d_mask; Cm.gamma = a->gamma;
-    for (int j = 0; j < 4; ++j) { Cm.low[j] = a->act_low[j]; Cm.high[j] = a->act_high[j]; }
-    Cm.k0 = (uint32_t)a->seed; Cm.k1 = (uint32_t)(a->seed >> 32); Cm.counter = a->d_counter;
+    fill_common(Cm, a, idx, n_part);
     float* stat = W + w.stat;
     auto policy_job = [&](int32_t* rows, uint32_t cnt_add) {
         return wide::AfJob{a->d_obs, nullptr, rows, a->d_ring_size, a->d_idx_in, cnt_add, W + w.a_pi, W + w.th, W + w.ah1, W + w.ah2};
@@ -608,8 +470,8 @@ static int enqueue_step(const scg_ddpg_args* a, hipStream_t st, int parity, bool
         wide::actor_fwd_kernel<<<dim3(n_part, 1), dim3(64 * NT), wide_lds_actor_fwd(), st>>>(a->d_params, a->actor, Cm, J, J);
     }
     // 2. q and dq/da at (obs, a)
-    wide::q_kernel<1><<<dim3(n_part, 1), dim3(64 * NT), wide_lds_q(), st>>>(a->d_params, nullptr, a->q, Cm, W + w.a_pi, nullptr, W + w.qpi,
-                                                                            W + w.dqda, QA, nullptr);
+    wide::q_kernel<1, QC><<<dim3(n_part, 1), dim3(64 * NT), wide_lds_q(), st>>>(a->d_params, nullptr, QC::Nets{a->q}, Cm, W + w.a_pi, QC::TgtArgs{}, W + w.qpi,
+                                                                                W + w.dqda, QA, nullptr);
     // 3. actor gradient
     wide::actor_grad_kernel<<<dim3(n_part), dim3(64 * NT), wide_lds_actor(), st>>>(a->d_params, a->actor, Cm, W + w.qpi, W + w.dqda, W + w.th,
                                                                                    W + w.ah1, W + w.ah2, W + w.partials);
@@ -622,11 +484,11 @@ static int enqueue_step(const scg_ddpg_args* a, hipStream_t st, int parity, bool
         wide::actor_fwd_kernel<<<dim3(n_part, with_next ? 2 : 1), dim3(64 * NT), wide_lds_actor_fwd(), st>>>(a->d_params, a->actor, Cm, J, Jn);
     }
     // 6. target critic at (next_obs, a'); beside it the online critic's forward pass at (obs, act)
-    wide::q_kernel<0><<<dim3(n_part, 2), dim3(64 * NT), wide_lds_q_fwd(), st>>>(a->d_target, a->d_params, a->q, Cm, W + w.a_next, nullptr, W + w.qt,
-                                                                                nullptr, QA, nullptr);
+    wide::q_kernel<0, QC><<<dim3(n_part, 2), dim3(64 * NT), wide_lds_q_fwd(), st>>>(a->d_target, a->d_params, QC::Nets{a->q}, Cm, W + w.a_next, QC::TgtArgs{},
+                                                                                    W + w.qt, nullptr, QA, nullptr);
     // 7. critic gradient
-    wide::q_kernel<2><<<dim3(n_part, 1), dim3(64 * NT), wide_lds_q(), st>>>(a->d_params, nullptr, a->q, Cm, nullptr, W + w.qt, nullptr, nullptr, QA,
-                                                                            W + w.partials);
+    wide::q_kernel<2, QC><<<dim3(n_part, 1), dim3(64 * NT), wide_lds_q(), st>>>(a->d_params, nullptr, QC::Nets{a->q}, Cm, nullptr, QC::TgtArgs{W + w.qt}, nullptr,
+                                                                                nullptr, QA, W + w.partials);
     // 8. its sum, the critic's Adam step, the soft update of the critic's target copy, the step's bookkeeping
     reduce_kernel<NQ, 1><<<dim3((Part<NQ, 1>::END + 63) / 64), dim3(256), 0, st>>>(reduce_args(a->q, a->critic_lr, 1));
     HIP_TRY(hipGetLastError());
@@ -634,13 +496,13 @@ static int enqueue_step(const scg_ddpg_args* a, hipStream_t st, int parity, bool
 }
 
 extern "C" int scg_ddpg_update(const scg_ddpg_args* a, void* stream) {
-    if (int rc = check_args(a, "scg_ddpg_update")) return rc;
+    if (int rc = check_step_args(a, "scg_ddpg_update")) return rc;
     if (int rc = scg_ddpg_prepare()) return rc;
     return enqueue_step(a, (hipStream_t)stream, 0, false, false);
 }
 
 extern "C" int scg_ddpg_update_n(const scg_ddpg_args* a, int n_steps, void* stream) {
-    if (int rc = check_args(a, "scg_ddpg_update_n")) return rc;
+    if (int rc = check_step_args(a, "scg_ddpg_update_n")) return rc;
     if (n_steps <= 0) return fail(-1, "scg_ddpg_update_n: n_steps must be positive");
     if (int rc = scg_ddpg_prepare()) return rc;
     for (int k = 0; k < n_steps; ++k)
@@ -668,9 +530,8 @@ static int launch_noisy(const float* d_params, const scg_mlp_layout* actor, cons
     if (noise && noise->kind != SCG_DDPG_NOISE_NONE &&
         (!noise->d_calls || !noise->d_pending || (noise->kind == SCG_DDPG_NOISE_OU && (!noise->d_x_prev || !noise->d_x_next))))
         return fail(-1, std::string(who) + ": noise state pointers missing");
-    float lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
-    for (int j = 0; j < NU; ++j) { lo[j] = act_low[j]; hi[j] = act_high[j]; }
-    const float4 l4 = make_float4(lo[0], lo[1], lo[2], lo[3]), h4 = make_float4(hi[0], hi[1], hi[2], hi[3]);
+    float4 l4, h4;
+    pack_bounds(act_low, act_high, l4, h4);
     if (uniform) {
         uniform_action_kernel<<<dim3((m + 255) / 256), dim3(256), 0, st>>>(m, l4, h4, (uint32_t)seed, (uint32_t)(seed >> 32), d_counter,
                                                                           noise ? noise->d_pending : nullptr, d_act_out);
@@ -709,15 +570,9 @@ extern "C" int scg_ddpg_noise_commit(const scg_ddpg_noise* noise, void* stream) 
 
 extern "C" int scg_ddpg_push(const scg_ddpg_ring* ring, const scg_ddpg_noise* noise, float* d_cur_obs, const float* d_act, const float* d_reward,
                              const float* d_next_obs, const float* d_terminal_obs, const uint8_t* d_done, const uint8_t* d_flags, int n, void* stream) {
-    if (!ring || !ring->d_obs || !ring->d_act || !ring->d_rew || !ring->d_next_obs || !ring->d_mask || !ring->d_pos || !d_cur_obs || !d_act ||
-        !d_reward || !d_next_obs || !d_terminal_obs || !d_done || !d_flags)
-        return fail(-1, "scg_ddpg_push: NULL argument");
-    if (n <= 0 || ring->capacity < n) return fail(-1, "scg_ddpg_push: replay capacity smaller than one vectorised step");
-    const RingArgs R{ring->d_obs, ring->d_act, ring->d_rew, ring->d_next_obs, ring->d_mask, ring->capacity, (long long*)ring->d_pos, ring->d_size_f,
-                     ring->d_size_i32, ring->d_counter};
-    const int total = n * NOBS;
-    ring_push_kernel<<<dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(R, d_cur_obs, d_act, d_reward, d_next_obs, d_terminal_obs,
-                                                                                       d_done, d_flags, n);
+    RingArgs R;
+    if (int rc = launch_ring_push(ring, d_cur_obs, d_act, d_reward, d_next_obs, d_terminal_obs, d_done, d_flags, n, (hipStream_t)stream, "scg_ddpg_push", R))
+        return rc;
     bookkeeping_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(R, 1, n, commit_args(noise));
     HIP_TRY(hipGetLastError());
     return 0;

@@ -7,6 +7,8 @@
 // other through tiny per-sample vectors (action, log-prob, q, dq/da: a few floats per row), which cross global memory between
 // launches.  Every MFMA kernel works on 32-sample column tiles, one tile per WORKGROUP, with the hidden layers split by feature
 // over the workgroup's waves (the wide tiles of scg_wide.h); all matrix products on v_mfma_f32_32x32x2_f32 (exact float32).
+// q_kernel, the pairing of reduce_kernel's group sums and the host helpers are scg_offpolicy_step.h's, shared with scg_ddpg.hip; the
+// actor kernels, the reductions' group sums and bookkeeping and the step sequence are this file's.
 //   actor_fwd_kernel     batch rows ~ U[0, ring size) (SACBuffer.sample :399-413), then
 //                        a, log pi (tanh-Gaussian, reparameterised)                       MLPActor.forward  (:185-222)
 //                        + what the policy gradient needs of this pass: the waves' h1 / h2 tiles, tanh u, sigma, the clamp's pass flags
@@ -84,18 +86,12 @@ extern "C" void scg_sac_shape(int32_t* nobs, int32_t* hidden, int32_t* nu, int32
 extern "C" const char* scg_sac_source_hash_tag(void) { return "SCG_SRC_HASH:" SCG_STR(SCG_SRC_HASH); }
 #define HIP_TRY(e) do { hipError_t _e = (e); if (_e != hipSuccess) return fail(-2, std::string(#e) + ": " + hipGetErrorString(_e)); } while (0)
 
+#define SCG_STEP_TEMPERATURE                    // wide::Common carries log_alpha
+#include "scg_offpolicy_step.h"
+
 constexpr float LOG_SQRT_2PI = 0.91893853320467274f, LOG2F = 0.69314718055994531f;
 
 // ------------------------------------------------------------------ kernels
-struct Common {
-    const int32_t* idx; int batch; int n_part;
-    const float* obs; const float* act; const float* rew; const float* next_obs; const float* mask;
-    float low[4], high[4];
-    const float* log_alpha;                     // device scalar (d_params + n_params)
-    float gamma;
-    uint32_t k0, k1; const uint32_t* counter;
-};
-
 __device__ __forceinline__ float softplusf(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 
 // tanh-Gaussian head (sac_utils.py:203-222 / sac.py::MLPActor.forward): out = mu | log_std
@@ -113,48 +109,24 @@ __device__ __forceinline__ void squash(const float* out, const float* eps, const
     }
 }
 
-// deterministic action of a batch (evaluation): a = low + 0.5 (tanh(mu) + 1)(high - low)
-__global__ __launch_bounds__(64 * WAVES, 1) void actor_act_kernel(const float* __restrict__ params, const scg_mlp_layout lay,
-                                                                   const float* __restrict__ obs, int m, float4 low, float4 high,
-                                                                   float* __restrict__ a_out) {
-    using L = MlpLds<NOBS, HID, NA>;
-    extern __shared__ __align__(16) float lds[];
-    mlp_fill_lds<NOBS, HID, NA>(lds, weights_of(params, lay), threadIdx.x);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-    const float lo[4] = {low.x, low.y, low.z, low.w}, hi[4] = {high.x, high.y, high.z, high.w};
-    const int n_tiles = (m + 31) / 32;
-    for (int tile = blockIdx.x * WAVES + wave; tile < n_tiles; tile += gridDim.x * WAVES) {
-        int s = tile * 32 + c;
-        const bool live = s < m;
-        s = live ? s : m - 1;
-        float x[L::L1Q];
-        load_x2<L::L1Q, NOBS, 0>(obs + (size_t)s * NOBS, nullptr, h, x);
-        f32x16 h1[NT], h2[NT];
-        float out[NA];
-        mlp_forward_tile<NOBS, HID, NA, ACT, 20, MLP_ACT_NONE>(lds, x, h1, h2, out, lane);
-        if (live && h == 0) {
-#pragma unroll
-            for (int j = 0; j < NU; ++j) a_out[(size_t)s * NU + j] = lo[j] + 0.5f * (tanhf(out[j]) + 1.0f) * (hi[j] - lo[j]);
-        }
-    }
-}
-
 // ================================================================== collector (SAC.train_step's env-facing half, sac.py:273-311)
-// A SAMPLED action of the policy for a batch of observations (MLPActorCritic.act(obs), sac_utils.py:258-262, deterministic = False):
-// a = low + 0.5 (tanh(mu + exp(clamp(log_std, -20, 2)) eps) + 1)(high - low), eps ~ N(0, 1) from Philox (counter word = *counter,
-// row, stream 3) or the caller's (tests).  One launch in place of ~12 PyTorch kernels (three GEMMs, activations, clamp, exp, randn, ...).
-__global__ __launch_bounds__(64 * WAVES, 1) void actor_sample_kernel(const float* __restrict__ params, const scg_mlp_layout lay,
-                                                                      const float* __restrict__ obs, int m, float4 low, float4 high,
-                                                                      uint32_t k0, uint32_t k1, const uint32_t* __restrict__ counter,
-                                                                      const float* __restrict__ eps_in, float* __restrict__ a_out) {
+// The policy's action for a batch of observations (MLPActorCritic.act(obs), sac_utils.py:258-262), one launch:
+//   SAMPLE = false (evaluation): deterministic, a = low + 0.5 (tanh(mu) + 1)(high - low); k0, k1, counter, eps_in unused
+//   SAMPLE = true  (collection): a = low + 0.5 (tanh(mu + exp(clamp(log_std, -20, 2)) eps) + 1)(high - low), eps ~ N(0, 1) from Philox
+//                  (counter word = *counter, row, stream 3) or the caller's (tests) — in place of ~12 PyTorch kernels (three GEMMs,
+//                  activations, clamp, exp, randn, ...)
+template <bool SAMPLE>
+__global__ __launch_bounds__(64 * WAVES, 1) void actor_kernel(const float* __restrict__ params, const scg_mlp_layout lay,
+                                                               const float* __restrict__ obs, int m, float4 low, float4 high,
+                                                               uint32_t k0, uint32_t k1, const uint32_t* __restrict__ counter,
+                                                               const float* __restrict__ eps_in, float* __restrict__ a_out) {
     using L = MlpLds<NOBS, HID, NA>;
     extern __shared__ __align__(16) float lds[];
     mlp_fill_lds<NOBS, HID, NA>(lds, weights_of(params, lay), threadIdx.x);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
     const float lo[4] = {low.x, low.y, low.z, low.w}, hi[4] = {high.x, high.y, high.z, high.w};
-    const uint32_t cnt = counter ? *counter : 0u;
+    const uint32_t cnt = SAMPLE && counter ? *counter : 0u;
     const int n_tiles = (m + 31) / 32;
     for (int tile = blockIdx.x * WAVES + wave; tile < n_tiles; tile += gridDim.x * WAVES) {
         int s = tile * 32 + c;
@@ -165,30 +137,30 @@ __global__ __launch_bounds__(64 * WAVES, 1) void actor_sample_kernel(const float
         f32x16 h1[NT], h2[NT];
         float out[NA], eps[4];
         mlp_forward_tile<NOBS, HID, NA, ACT, 20, MLP_ACT_NONE>(lds, x, h1, h2, out, lane);
-        if (eps_in) {
+        if constexpr (SAMPLE) {
+            if (eps_in) {
 #pragma unroll
-            for (int j = 0; j < NU; ++j) eps[j] = eps_in[(size_t)s * NU + j];
-        } else {
-            normal4(cnt, (uint32_t)s, 3u, k0, k1, eps);
+                for (int j = 0; j < NU; ++j) eps[j] = eps_in[(size_t)s * NU + j];
+            } else {
+                normal4(cnt, (uint32_t)s, 3u, k0, k1, eps);
+            }
         }
         if (live && h == 0) {
 #pragma unroll
             for (int j = 0; j < NU; ++j) {
-                const float ls = fminf(fmaxf(out[NU + j], -20.0f), 2.0f);
-                const float u = __builtin_fmaf(expf(ls), eps[j], out[j]);
+                float u = out[j];
+                if constexpr (SAMPLE) u = __builtin_fmaf(expf(fminf(fmaxf(out[NU + j], -20.0f), 2.0f)), eps[j], out[j]);
                 a_out[(size_t)s * NU + j] = lo[j] + 0.5f * (tanhf(u) + 1.0f) * (hi[j] - lo[j]);
             }
         }
     }
 }
+constexpr size_t LDS_ACTOR = MlpLds<NOBS, HID, NA>::END * sizeof(float);         // the LDS weight image: what both launches pass
 
 // The ring's write position behind ring_push_kernel (scg_wide.h), which every thread of that launch reads.
 __global__ void ring_advance_kernel(const RingArgs R, int n) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    *R.pos = (*R.pos + n) % R.capacity;
-    if (R.size_f) *R.size_f = fminf(*R.size_f + (float)n, (float)R.capacity);
-    if (R.size_i) *R.size_i = min(*R.size_i + n, R.capacity);
-    if (R.counter) *R.counter += 1u;
+    ring_advance(R, n);
 }
 
 // ================================================================== gradient step (the wide-tile scheme: scg_wide.h)
@@ -282,141 +254,21 @@ __global__ __launch_bounds__(64 * NT, 2) void actor_fwd_kernel(const float* __re
     }
 }
 
-// Q networks.
-//   MODE 0: forward only, blockIdx.y = y + 2 * online:
-//             online = 0: TARGET network y at (next_obs[idx], a_in[row])          -> q_out[y][row]
-//             online = 1: ONLINE network y at (obs[idx], act[idx])                -> qo[y][row] and the waves' h1 / h2 tiles, for MODE 2
-//           (the second kind does not depend on the first: it is the forward half of the critic loss, run here next to the targets
-//            instead of behind them)
-//   MODE 1: online networks at (obs[idx], a_in[row]), data gradient       -> q_out[y][row], dqda[y][row][NU]; blockIdx.y = y
-//   MODE 2: backward only, blockIdx.y = y: d mean (q - y)^2 / d(theta_y) into the workgroups' partials, q = qo[y][row] and the stored
-//           tiles, y = rew + gamma mask (min(qt1, qt2) - alpha logp_next)
-struct QAct { float* qo; float* h1s; float* h2s; float* rew; float* mask; };     // [2][B], [2][B / 32 tiles][NT][1024] each, [B], [B]
-template <int MODE>
-__global__ __launch_bounds__(64 * NT, MODE == 0 ? 2 : 1) void q_kernel(const float* __restrict__ params, const float* __restrict__ params_online,
-                                                        const scg_mlp_layout lay1, const scg_mlp_layout lay2,
-                                                        const Common Cm, const float* __restrict__ a_in, const float* __restrict__ qt,
-                                                        const float* __restrict__ logp_next, float* __restrict__ q_out,
-                                                        float* __restrict__ dqda, const QAct QA, float* __restrict__ partials) {
-    using S = Small<1>;
-    using G = Part<NQ, 1>;
-    constexpr int L1Q = 4 * ((NQ + 7) / 8);
-    extern __shared__ __align__(16) float lds[];
-    const int y = blockIdx.y & 1;
-    const bool online = MODE == 0 && (blockIdx.y >> 1);
-    const MlpWeights w = weights_of(online ? params_online : params, y ? lay2 : lay1);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 31, h = lane >> 5;
-    const int n_tiles = Cm.batch / 32, B = Cm.batch;
-    const int tile0 = blockIdx.x, r0 = tile0 * 32 + c;
-    const int s0 = Cm.idx[r0];                                          // (gridDim.x <= n_tiles; unconditional: see actor_grad_kernel)
-    SmallRegs<1> sr;
-    small_load<1>(sr, w, threadIdx.x);
-    float* const xch = lds + S::END;
-    if constexpr (MODE == 2) {
-        // ---- backward only.  Request order: row index, small block, the tiles and the row's values, the data-gradient operand
-        float bt[NT][16];
-        const float* const h1s = QA.h1s + (size_t)y * B * HID;
-        const float* const h2s = QA.h2s + (size_t)y * B * HID;
-        f32x16 h1, h2;
-        float x[L1Q], v_rew = 0.0f, v_mask = 0.0f, v_qt1 = 0.0f, v_qt2 = 0.0f, v_lpn = 0.0f, v_q = 0.0f;
-        // (reward and mask by BATCH row, left by q_kernel<0>'s online blocks: nothing the loss derivative needs waits for the row index)
-        auto load_row = [&](int tile, int r) {
-            act_load(h1s, tile, wave, lane, h1); act_load(h2s, tile, wave, lane, h2);
-            v_q = QA.qo[(size_t)y * B + r]; v_qt1 = qt[r]; v_qt2 = qt[B + r]; v_lpn = logp_next[r];
-            v_rew = QA.rew[r]; v_mask = QA.mask[r];
-        };
-        auto load_in = [&](int s) { load_x2<L1Q, NOBS, NU>(Cm.obs + (size_t)s * NOBS, Cm.act + (size_t)s * NU, h, x); };
-        load_row(tile0, r0);
-        load_bt(w.W2, wave, lane, bt);                                  // (see actor_grad_kernel)
-        load_in(s0);
-        small_store<1>(lds, sr, threadIdx.x);
-        __syncthreads();
-        float* const P = partials + ((size_t)y * Cm.n_part + blockIdx.x) * PSTRIDE;
-        const float alpha = expf(*Cm.log_alpha);
-        const float inv_b = 1.0f / (float)B;
-        float st = 0.0f;
-        bool first = true;
-        for (int tile = tile0; tile < n_tiles; tile += gridDim.x) {
-            const int r = tile * 32 + c;
-            if (tile != tile0) { load_row(tile, r); load_in(Cm.idx[r]); }
-            const float target = v_rew + Cm.gamma * v_mask * (fminf(v_qt1, v_qt2) - alpha * v_lpn);
-            const float e = v_q - target;
-            const float dout[1] = {2.0f * e * inv_b};
-            if (wave == 0 && h == 0) st += e * e * inv_b;
-            backward<NQ, 1, ACT, true, false>(lds, xch, bt, h1, h2, dout, wave, lane, P, first, nullptr, x);
-            first = false;
-            __syncthreads();                                            // the exchange buffers are free for the next tile
+// The critics' side of q_kernel (scg_offpolicy_step.h): two of them, target = rew + gamma mask (min(qt1, qt2) - alpha logp_next).
+struct SacCritics {
+    static constexpr int NCRIT = 2;
+    struct Nets { scg_mlp_layout lay1, lay2; };
+    static __device__ __forceinline__ const scg_mlp_layout& layout(const Nets& N, int y) { return y ? N.lay2 : N.lay1; }
+    struct TgtArgs { const float* __restrict__ qt; const float* __restrict__ logp_next; };      // [2][B], [B]
+    struct Tgt {
+        float qt1 = 0.0f, qt2 = 0.0f, lpn = 0.0f, alpha = 0.0f;
+        __device__ __forceinline__ void load(const TgtArgs& A, int r, int B) { qt1 = A.qt[r]; qt2 = A.qt[B + r]; lpn = A.logp_next[r]; }
+        __device__ __forceinline__ void init(const Common& Cm) { alpha = expf(*Cm.log_alpha); }
+        __device__ __forceinline__ float value(const Common& Cm, float v_rew, float v_mask) const {
+            return v_rew + Cm.gamma * v_mask * (fminf(qt1, qt2) - alpha * lpn);
         }
-        if (wave == 0) {                                                // (st lives in the lanes of half 0)
-            const float v = row_sum32(xch + Xch::WAVE + TR_WORDS + 34 * 32, st, lane);
-            if (lane == 0) { P[G::STAT] = v; P[G::STAT + 1] = 0.0f; }
-        }
-    } else {
-        // request order (see small_load): the first tile's row index, the small block, the forward operands, the row's values;
-        // the backward operand (bt) is requested behind the barrier and arrives under the forward pass
-        float w1a[(NU * HID + 64 * NT - 1) / (64 * NT)];
-        if constexpr (MODE == 1) {                                      // W1A[j][f] = W1[f][NOBS + j]
-#pragma unroll
-            for (int j = 0; j < (NU * HID + 64 * NT - 1) / (64 * NT); ++j) {
-                const int k = threadIdx.x + j * 64 * NT;
-                w1a[j] = k < NU * HID ? w.W1[(size_t)(k % HID) * NQ + NOBS + k / HID] : 0.0f;
-            }
-        }
-        float a1[L1Q], a2[NT][16];
-        load_a1<NQ, L1Q>(w.W1, wave, lane, a1);
-        load_a2(w.W2, wave, lane, a2);
-        float x[L1Q], v_rew = 0.0f, v_mask = 0.0f;
-        auto load_row = [&](int r, int s) {
-            if constexpr (MODE == 0) {
-                if (online) {
-                    load_x2<L1Q, NOBS, NU>(Cm.obs + (size_t)s * NOBS, Cm.act + (size_t)s * NU, h, x);
-                    if (y == 0) { v_rew = Cm.rew[s]; v_mask = Cm.mask[s]; }
-                } else load_x2<L1Q, NOBS, NU>(Cm.next_obs + (size_t)s * NOBS, a_in + (size_t)r * NU, h, x);
-            } else {
-                load_x2<L1Q, NOBS, NU>(Cm.obs + (size_t)s * NOBS, a_in + (size_t)r * NU, h, x);
-            }
-        };
-        load_row(r0, s0);
-        small_store<1>(lds, sr, threadIdx.x);
-        if constexpr (MODE == 1) {
-#pragma unroll
-            for (int j = 0; j < (NU * HID + 64 * NT - 1) / (64 * NT); ++j) {
-                const int k = threadIdx.x + j * 64 * NT;
-                if (k < NU * HID) lds[S::W1A + k] = w1a[j];
-            }
-        }
-        __syncthreads();
-        float bt[MODE == 1 ? NT : 1][16];
-        if constexpr (MODE == 1) load_bt(w.W2, wave, lane, bt);
-        for (int tile = tile0; tile < n_tiles; tile += gridDim.x) {
-            const int r = tile * 32 + c;
-            if (tile != tile0) load_row(r, Cm.idx[r]);
-            f32x16 h1, h2;
-            float out[1];
-            forward<NQ, 1, ACT>(lds, xch, a1, a2, x, wave, lane, h1, h2, out);
-            if constexpr (MODE == 0) {
-                if (online) {
-                    act_store(QA.h1s + (size_t)y * B * HID, tile, wave, lane, h1);
-                    act_store(QA.h2s + (size_t)y * B * HID, tile, wave, lane, h2);
-                    if (wave == 0 && h == 0) QA.qo[(size_t)y * B + r] = out[0];
-                    if (wave == 1 % NT && h == 0 && y == 0) { QA.rew[r] = v_rew; QA.mask[r] = v_mask; }
-                } else if (wave == 0 && h == 0) {
-                    q_out[(size_t)y * B + r] = out[0];
-                }
-            } else {
-                const float dout[1] = {1.0f};
-                float din[NU];
-                backward<NQ, 1, ACT, false, true>(lds, xch, bt, h1, h2, dout, wave, lane, nullptr, true, din);
-                if (wave == 0 && h == 0) {
-                    q_out[(size_t)y * B + r] = out[0];
-#pragma unroll
-                    for (int j = 0; j < NU; ++j) dqda[((size_t)y * B + r) * NU + j] = din[j];
-                }
-                __syncthreads();                                        // the exchange buffers are free for the next tile
-            }
-        }
-    }
-}
+    };
+};
 
 // actor gradient of policy_loss = mean(alpha log pi - min(q1, q2)(obs, a)), from the pass actor_fwd_kernel left behind: the waves' h1 / h2
 // tiles, the head's (tanh u, sigma, clamp pass), log pi and the noise.  Request order: row index, small block (W3 for dz2), the tiles,
@@ -543,7 +395,9 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceArgs R) {
     constexpr int words = Part<NIN, NOUT>::END;
     // Request order: what the word's OWNER needs for its optimiser step (parameter, moments, target copy, step count) goes out first and
     // arrives under the partial loads — asked for behind the sum it was one more memory round trip at the end of every block; then ALL
-    // of this thread's partial words at once (32 at n_part = 128; `unroll 8` made that four rounds of eight).  The sum keeps its order.
+    // of this thread's partial words at once (32 at n_part = 128; `unroll 8` made that four rounds of eight).  The sum keeps its order:
+    // this loop is word for word scg_ddpg.hip's (as a shared device function it reshaped both kernels' loops and register use: not
+    // shown to be free, so it stays written out), the pairing behind the barrier is pair_sum (scg_offpolicy_step.h).
     const bool owner = grp == 0 && k < words;
     int d = -1;
     float o_p = 0.0f, o_m = 0.0f, o_v = 0.0f, o_t = 0.0f, o_steps = 0.0f;
@@ -590,7 +444,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceArgs R) {
     }
     __syncthreads();
     if (!owner) return;
-    s = (part[0][kl] + part[1][kl]) + (part[2][kl] + part[3][kl]);
+    s = pair_sum(&part[0][kl], sizeof part[0] / sizeof part[0][0]);
     if (d >= 0) {
         R.grad[d] = s;
         if (R.p) {
@@ -614,7 +468,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const ReduceArgs R) {
                 for (int g = q; g < R.n_part; g += 4) o += other[g];
                 o4[q] = o;
             }
-            const float cl = s + ((o4[0] + o4[1]) + (o4[2] + o4[3]));
+            const float cl = s + pair_sum(o4, 1);
             const float el = F.alpha_on ? -f_la * (ml + F.target_entropy) : 0.0f;
             F.stats[0] = pl; F.stats[1] = cl; F.stats[2] = el; F.stats[3] = ml;
             if (F.stats_acc) { F.stats_acc[0] = f_acc[0] + pl; F.stats_acc[1] = f_acc[1] + cl; F.stats_acc[2] = f_acc[2] + el; F.stats_acc[3] = f_acc[3] + ml; }
@@ -673,7 +527,8 @@ __global__ void finish_kernel(const FinishArgs F) {
     if (F.stats_acc) { F.stats_acc[0] += pl; F.stats_acc[1] += cl; F.stats_acc[2] += el; F.stats_acc[3] += ml; }
 }
 
-// ------------------------------------------------------------------ host side
+// ------------------------------------------------------------------ host side (with the helpers of scg_offpolicy_step.h)
+using QC = wide::SacCritics;
 struct Ws {      // workspace carve-up (floats)
     size_t idx[2], eps, a_pi, logp, eps2, a_next, logp_next, qpi, dqda, qt, stat, la_before[2], head, ah1, ah2, qo, qh1, qh2, qrew, qmask, partials, total;
 };
@@ -691,25 +546,11 @@ static Ws carve(int B, int n_part) {
     w.total = o;
     return w;
 }
-static int n_part_of(int batch) { const int t = batch / 32; return t < 512 ? t : 512; }
 
 extern "C" size_t scg_sac_workspace_bytes(int batch) {
     if (batch <= 0 || batch % 32) return 0;
     return carve(batch, n_part_of(batch)).total * sizeof(float);
 }
-
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-    HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
-
-static size_t lds_actor_bytes() { return (MlpLds<NOBS, HID, NA>::END + WAVES * (32 * ((NOBS + 3) / 4 * 4) + NA * 32 + TR_WORDS)) * sizeof(float); }
-static size_t wide_lds_actor() { return (wide::Small<NA>::END + wide::Xch::END) * sizeof(float); }
-static size_t wide_lds_q() { return (wide::Small<1>::END + wide::Xch::END) * sizeof(float); }
-// forward-only launches need the small block, the h1 exchange and the output partials only: two workgroups per CU fit
-static size_t wide_lds_actor_fwd() { return (wide::Small<NA>::END + wide::Xch::FWD_END) * sizeof(float); }
-static size_t wide_lds_q_fwd() { return (wide::Small<1>::END + wide::Xch::FWD_END) * sizeof(float); }
 
 // One-time kernel attributes (dynamic LDS above 64 KB).  Call once before capturing scg_sac_update into a HIP graph: the
 // attribute calls are not stream operations.  scg_sac_update calls it itself otherwise.
@@ -717,21 +558,12 @@ extern "C" int scg_sac_prepare(void) {
     static scg::PerDeviceOnce once;         // per device (scg_once.h): call with the agent's device current
     int dev;
     if (!once.pending(&dev)) return 0;
-    const size_t lds_a = lds_actor_bytes();
-    if (lds_a > 160 * 1024 || wide_lds_actor() > 160 * 1024 || wide_lds_q() > 160 * 1024)
+    if (LDS_ACTOR > 160 * 1024 || wide_lds_actor() > 160 * 1024 || wide_lds_q() > 160 * 1024)
         return fail(-1, "scg_sac: network image does not fit the LDS");
-    if (set_lds(actor_act_kernel, lds_a) || set_lds(actor_sample_kernel, MlpLds<NOBS, HID, NA>::END * sizeof(float))) return -2;
+    if (set_lds(actor_kernel<false>, LDS_ACTOR) || set_lds(actor_kernel<true>, LDS_ACTOR)) return -2;
     if (set_lds(wide::actor_fwd_kernel, wide_lds_actor_fwd()) || set_lds(wide::actor_grad_kernel, wide_lds_actor()) ||
-        set_lds(wide::q_kernel<0>, wide_lds_q_fwd()) || set_lds(wide::q_kernel<1>, wide_lds_q()) || set_lds(wide::q_kernel<2>, wide_lds_q())) return -2;
+        set_lds(wide::q_kernel<0, QC>, wide_lds_q_fwd()) || set_lds(wide::q_kernel<1, QC>, wide_lds_q()) || set_lds(wide::q_kernel<2, QC>, wide_lds_q())) return -2;
     once.commit(dev);
-    return 0;
-}
-
-static int check_args(const scg_sac_args* a, const char* who) {
-    if (!a || !a->d_params || !a->d_target || !a->d_grad || !a->d_m || !a->d_v || !a->d_steps || !a->d_obs || !a->d_act || !a->d_rew ||
-        !a->d_next_obs || !a->d_mask || !a->d_counter || !a->d_workspace || !a->d_stats || (!a->d_ring_size && !a->d_idx_in))
-        return fail(-1, std::string(who) + ": NULL argument");
-    if (a->batch <= 0 || a->batch % 32) return fail(-1, std::string(who) + ": the batch size must be a positive multiple of 32");
     return 0;
 }
 
@@ -746,11 +578,9 @@ static int enqueue_step(const scg_sac_args* a, hipStream_t st, int phases, int p
     int32_t* idx_next = (int32_t*)(W + w.idx[parity ^ 1]);
     float* la_before = W + w.la_before[parity];
     const size_t wlds_a = wide_lds_actor(), wlds_q = wide_lds_q(), wlds_af = wide_lds_actor_fwd(), wlds_qf = wide_lds_q_fwd();
-    Common Cm;
-    Cm.idx = idx; Cm.batch = B; Cm.n_part = n_part; Cm.obs = a->d_obs; Cm.act = a->d_act; Cm.rew = a->d_rew; Cm.next_obs = a->d_next_obs;
-    Cm.mask = a->d_mask; Cm.log_alpha = a->d_params + a->n_params; Cm.gamma = a->gamma;
-    for (int j = 0; j < 4; ++j) { Cm.low[j] = a->act_low[j]; Cm.high[j] = a->act_high[j]; }
-    Cm.k0 = (uint32_t)a->seed; Cm.k1 = (uint32_t)(a->seed >> 32); Cm.counter = a->d_counter;
+    wide::Common Cm;
+    fill_common(Cm, a, idx, n_part);
+    Cm.log_alpha = a->d_params + a->n_params;
     float* stat = W + w.stat;
     // the whole step on one GPU: the optimiser steps ride in the reduction launches; data-parallel callers (phases given one
     // by one, an all-reduce of d_grad between them) get the gradient only and step in adam_kernel
@@ -781,7 +611,7 @@ static int enqueue_step(const scg_sac_args* a, hipStream_t st, int phases, int p
         wide::actor_fwd_kernel<<<dim3(n_part, 1), dim3(64 * NT), wlds_af, st>>>(a->d_params, a->actor, Cm, J, J);
     }
     // 2. q1, q2 and dq/da at (obs, a)
-    wide::q_kernel<1><<<dim3(n_part, 2), dim3(64 * NT), wlds_q, st>>>(a->d_params, nullptr, a->q1, a->q2, Cm, W + w.a_pi, nullptr, nullptr, W + w.qpi, W + w.dqda, QA, nullptr);
+    wide::q_kernel<1, QC><<<dim3(n_part, 2), dim3(64 * NT), wlds_q, st>>>(a->d_params, nullptr, QC::Nets{a->q1, a->q2}, Cm, W + w.a_pi, QC::TgtArgs{}, W + w.qpi, W + w.dqda, QA, nullptr);
     // 3. actor gradient
     wide::actor_grad_kernel<<<dim3(n_part), dim3(64 * NT), wlds_a, st>>>(a->d_params, a->actor, Cm, W + w.eps, W + w.qpi, W + w.dqda, W + w.head, W + w.logp,
                                                                          W + w.ah1, W + w.ah2, W + w.partials);
@@ -808,9 +638,9 @@ static int enqueue_step(const scg_sac_args* a, hipStream_t st, int phases, int p
         wide::actor_fwd_kernel<<<dim3(n_part, with_next ? 2 : 1), dim3(64 * NT), wlds_af, st>>>(a->d_params, a->actor, Cm, J, Jn);
     }
     // 6. target networks at (next_obs, a'); next to them the online critics' forward pass at (obs, act) for 7
-    wide::q_kernel<0><<<dim3(n_part, 4), dim3(64 * NT), wlds_qf, st>>>(a->d_target, a->d_params, a->q1, a->q2, Cm, W + w.a_next, nullptr, nullptr, W + w.qt, nullptr, QA, nullptr);
+    wide::q_kernel<0, QC><<<dim3(n_part, 4), dim3(64 * NT), wlds_qf, st>>>(a->d_target, a->d_params, QC::Nets{a->q1, a->q2}, Cm, W + w.a_next, QC::TgtArgs{}, W + w.qt, nullptr, QA, nullptr);
     // 7. critic gradients
-    wide::q_kernel<2><<<dim3(n_part, 2), dim3(64 * NT), wlds_q, st>>>(a->d_params, nullptr, a->q1, a->q2, Cm, nullptr, W + w.qt, W + w.logp_next, nullptr, nullptr, QA, W + w.partials);
+    wide::q_kernel<2, QC><<<dim3(n_part, 2), dim3(64 * NT), wlds_q, st>>>(a->d_params, nullptr, QC::Nets{a->q1, a->q2}, Cm, nullptr, QC::TgtArgs{W + w.qt, W + w.logp_next}, nullptr, nullptr, QA, W + w.partials);
     // 8. their sums (+ the critic steps and the soft update of their target copies when fused)
     {
         ReduceArgs R; R.partials = W + w.partials; R.n_part = n_part; R.lay[0] = a->q1; R.lay[1] = a->q2; R.grad = a->d_grad; R.stat_out = stat + 2;
@@ -837,7 +667,7 @@ static int enqueue_step(const scg_sac_args* a, hipStream_t st, int phases, int p
 }
 
 extern "C" int scg_sac_update(const scg_sac_args* a, void* stream) {
-    if (int rc = check_args(a, "scg_sac_update")) return rc;
+    if (int rc = check_step_args(a, "scg_sac_update")) return rc;
     if (int rc = scg_sac_prepare()) return rc;
     return enqueue_step(a, (hipStream_t)stream, a->phases == 0 ? SCG_SAC_ALL : a->phases, 0, false, false);
 }
@@ -846,7 +676,7 @@ extern "C" int scg_sac_update(const scg_sac_args* a, void* stream) {
 // 7 n_steps + 1 launches instead of 8 n_steps: the target-action launch of step k also runs step k + 1's first launch (see
 // wide::actor_fwd_kernel) — nothing between the two touches the actor, the replay ring or the row draw's inputs.
 extern "C" int scg_sac_update_n(const scg_sac_args* a, int n_steps, void* stream) {
-    if (int rc = check_args(a, "scg_sac_update_n")) return rc;
+    if (int rc = check_step_args(a, "scg_sac_update_n")) return rc;
     if (n_steps <= 0) return fail(-1, "scg_sac_update_n: n_steps must be positive");
     if (a->phases != 0 && a->phases != SCG_SAC_ALL) return fail(-1, "scg_sac_update_n: whole steps only (phases = 0)");
     if (int rc = scg_sac_prepare()) return rc;
@@ -858,17 +688,15 @@ extern "C" int scg_sac_update_n(const scg_sac_args* a, int n_steps, void* stream
 extern "C" int scg_sac_sample(const float* d_params, const scg_mlp_layout* actor, const float* act_low, const float* act_high, const float* d_obs,
                               int m, uint64_t seed, const uint32_t* d_counter, int uniform, const float* d_eps_in, float* d_act_out, void* stream) {
     if (!act_low || !act_high || !d_act_out || m <= 0 || (!uniform && (!d_params || !actor || !d_obs))) return fail(-1, "scg_sac_sample: bad argument");
-    float lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
-    for (int j = 0; j < NU; ++j) { lo[j] = act_low[j]; hi[j] = act_high[j]; }
-    const float4 l4 = make_float4(lo[0], lo[1], lo[2], lo[3]), h4 = make_float4(hi[0], hi[1], hi[2], hi[3]);
+    float4 l4, h4;
+    pack_bounds(act_low, act_high, l4, h4);
     if (uniform) {
         uniform_action_kernel<<<dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(m, l4, h4, (uint32_t)seed, (uint32_t)(seed >> 32), d_counter, nullptr, d_act_out);
     } else {
-        const size_t lds_a = MlpLds<NOBS, HID, NA>::END * sizeof(float);
         if (int rc = scg_sac_prepare()) return rc;
         const int grid = std::min(256, (m + 127) / 128);
-        actor_sample_kernel<<<dim3(grid), dim3(64 * WAVES), lds_a, (hipStream_t)stream>>>(d_params, *actor, d_obs, m, l4, h4, (uint32_t)seed,
-                                                                                            (uint32_t)(seed >> 32), d_counter, d_eps_in, d_act_out);
+        actor_kernel<true><<<dim3(grid), dim3(64 * WAVES), LDS_ACTOR, (hipStream_t)stream>>>(d_params, *actor, d_obs, m, l4, h4, (uint32_t)seed,
+                                                                                             (uint32_t)(seed >> 32), d_counter, d_eps_in, d_act_out);
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -876,14 +704,9 @@ extern "C" int scg_sac_sample(const float* d_params, const scg_mlp_layout* actor
 
 extern "C" int scg_sac_push(const scg_sac_ring* ring, float* d_cur_obs, const float* d_act, const float* d_reward, const float* d_next_obs,
                             const float* d_terminal_obs, const uint8_t* d_done, const uint8_t* d_flags, int n, void* stream) {
-    if (!ring || !ring->d_obs || !ring->d_act || !ring->d_rew || !ring->d_next_obs || !ring->d_mask || !ring->d_pos || !d_cur_obs || !d_act ||
-        !d_reward || !d_next_obs || !d_terminal_obs || !d_done || !d_flags)
-        return fail(-1, "scg_sac_push: NULL argument");
-    if (n <= 0 || ring->capacity < n) return fail(-1, "scg_sac_push: replay capacity smaller than one vectorised step");
-    const RingArgs R{ring->d_obs, ring->d_act, ring->d_rew, ring->d_next_obs, ring->d_mask, ring->capacity, (long long*)ring->d_pos, ring->d_size_f,
-                     ring->d_size_i32, ring->d_counter};
-    const int total = n * NOBS;
-    ring_push_kernel<<<dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream>>>(R, d_cur_obs, d_act, d_reward, d_next_obs, d_terminal_obs, d_done, d_flags, n);
+    RingArgs R;
+    if (int rc = launch_ring_push(ring, d_cur_obs, d_act, d_reward, d_next_obs, d_terminal_obs, d_done, d_flags, n, (hipStream_t)stream, "scg_sac_push", R))
+        return rc;
     ring_advance_kernel<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(R, n);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -892,13 +715,11 @@ extern "C" int scg_sac_push(const scg_sac_ring* ring, float* d_cur_obs, const fl
 extern "C" int scg_sac_act(const float* d_params, const scg_mlp_layout* actor, const float* act_low, const float* act_high, const float* d_obs,
                            int m, float* d_act_out, void* stream) {
     if (!d_params || !actor || !act_low || !act_high || !d_obs || !d_act_out || m <= 0) return fail(-1, "scg_sac_act: bad argument");
-    const size_t lds_a = MlpLds<NOBS, HID, NA>::END * sizeof(float);
     if (int rc = scg_sac_prepare()) return rc;
-    float lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
-    for (int j = 0; j < NU; ++j) { lo[j] = act_low[j]; hi[j] = act_high[j]; }
+    float4 l4, h4;
+    pack_bounds(act_low, act_high, l4, h4);
     const int grid = std::min(256, (m + 127) / 128);
-    actor_act_kernel<<<dim3(grid), dim3(64 * WAVES), lds_a, (hipStream_t)stream>>>(d_params, *actor, d_obs, m, make_float4(lo[0], lo[1], lo[2], lo[3]),
-                                                                                     make_float4(hi[0], hi[1], hi[2], hi[3]), d_act_out);
+    actor_kernel<false><<<dim3(grid), dim3(64 * WAVES), LDS_ACTOR, (hipStream_t)stream>>>(d_params, *actor, d_obs, m, l4, h4, 0u, 0u, nullptr, nullptr, d_act_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,7 +1,8 @@
 // scg_wide.h — the wide-tile MLP passes of the fused off-policy gradient steps, and the collector kernels the off-policy agents
 // share: the one home of the scheme, included by libscg_sac_* (scg_sac.hip) and libscg_ddpg_* (scg_ddpg.hip).  What differs between
-// the algorithms — the step's kernels (two critics and a temperature against one critic), the loss heads, the host side — stays in
-// the two .hip files; an edit here makes both libraries stale (_sac.DEPS, _ddpg.DEPS).
+// the algorithms — the actor kernels and loss heads, the reductions' bookkeeping, the step sequences — stays in the two .hip files;
+// what the steps share on top of these passes (the critic kernel, the host helpers) is scg_offpolicy_step.h.  An edit here makes
+// both libraries stale (_sac.DEPS, _ddpg.DEPS).
 // Include AFTER defining the network constants: NOBS, HID, NU, ACT, NQ (= NOBS + NU), NA (actor head width), NT (= HID / 32),
 // and SCG_S_STAMP (a no-op outside scg_sac.hip's timing builds).
 #pragma once

@@ -213,8 +213,9 @@ def test_sac_collector_reproduces_the_reference_buffer(device, norm):
 
 
 def test_wide_tile_code_has_one_home_and_every_include_is_hashed():
-    """scg_wide.h is the only definition of the wide-tile passes, and every header the SAC and DDPG libraries include — directly or
-    through it — is in their DEPS, so that editing one makes the libraries stale."""
+    """scg_wide.h is the only definition of the wide-tile passes and scg_offpolicy_step.h the only one of what the two steps share
+    beyond them, and every header the SAC and DDPG libraries include — directly or through those two — is in their DEPS, so that
+    editing one makes the libraries stale."""
     import os
     import re
     from safe_control_gym_amd import _ddpg, _sac
@@ -223,12 +224,14 @@ def test_wide_tile_code_has_one_home_and_every_include_is_hashed():
         with open(path) as f:
             return {os.path.normpath(os.path.join(os.path.dirname(path), name)) for name in re.findall(r'#include "([^"]+)"', f.read())}
     wide = os.path.join(os.path.dirname(_sac.SRC), 'scg_wide.h')
+    step = os.path.join(os.path.dirname(_sac.SRC), 'scg_offpolicy_step.h')
     for mod in (_sac, _ddpg):
         deps = {os.path.normpath(p) for p in mod.DEPS}
-        assert wide in includes(mod.SRC)
-        missing = (includes(mod.SRC) | includes(wide)) - deps
+        assert wide in includes(mod.SRC) and step in includes(mod.SRC)
+        missing = (includes(mod.SRC) | includes(wide) | includes(step)) - deps
         assert not missing, f'{os.path.basename(mod.SRC)}: not in DEPS: {sorted(missing)}'
-    with open(_sac.SRC) as f:
-        sac = f.read()
-    for definition in ('struct Part', 'store_wt(', 'struct Xch', 'void backward('):
-        assert definition not in sac, f'scg_sac.hip defines {definition!r} again'
+        with open(mod.SRC) as f:
+            text = f.read()
+        for definition in ('struct Part', 'store_wt(', 'struct Xch', 'void backward(',
+                           'void q_kernel(', 'struct QAct', 'int n_part_of(', 'size_t wide_lds_q('):
+            assert definition not in text, f'{os.path.basename(mod.SRC)} defines {definition!r} again'
